@@ -5,12 +5,16 @@ cluster segmentation (ImageProjection) + curvature / feature extraction (Feature
 feature stage), labels / feature indices bit-exact vs the CPU path. A "step" is one pass of the
 hot path over one batch of B scans per GPU that is already resident in HBM.
 
-The same JSON line carries a second measured leg, "scan2map" (BASELINE.json configs[2]): batches
-of P scan-to-map problems (MapOptimization::scan2MapOptimization) against the ~100k-point local
-map of tests/golden/mo_map_vlp16.npz, in lm_applied and faithful (200-iteration) mode, with the
-pose delta against the CPU restatement and its own CPU baseline.
+A plain run sets up, warms up, times the K steps and prints the headline JSON line; with
+--dump-outputs DIR it also writes the last timed step's outputs as DIR/<name>.npy.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+With --full the same JSON line also carries the per-kernel profiling pass and rooflines, the parity
+spot check, the CPU baselines and the side legs, first of them "scan2map" (BASELINE.json
+configs[2]): batches of P scan-to-map problems (MapOptimization::scan2MapOptimization) against
+the ~100k-point local map of tests/golden/mo_map_vlp16.npz, in lm_applied and faithful
+(200-iteration) mode, with the pose delta against the CPU restatement and its own CPU baseline.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by torch.distributed.run (one rank per GPU). Scans are batch-sharded: every
 rank processes its own B scans with no data-path collective (weak scaling); ranks only meet at the
@@ -827,6 +831,35 @@ def pc2_decode_leg(dev, pts: np.ndarray, off: np.ndarray, steps: int, dist) -> d
             "algorithmic_GBs_incl_host_sync": round(gbs, 1), "bit_exact": exact}
 
 
+DUMP_SLOTS = 8  # scans of the batch whose arrays --dump-outputs writes
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir: str, pipe, B: int) -> None:
+    """--dump-outputs: what a caller of process_batch receives from the handle that ran the last
+    timed step. counts.npy is batch_counts() of all B scans; every other file is one array of
+    fetch() (its per-scan counts as scan_counts.npy, one row per scan) concatenated over a fixed
+    seeded sample of the batch's scans, listed in sample_slots.npy. Float arrays stay float32,
+    integer arrays are written as float64 (exact)."""
+    from llsr import _abi
+    H, W = pipe.cfg.num_vertical_scans, pipe.cfg.num_horizontal_scans
+    # upper bound of one scan's arrays as written, so the sample fits the size limit whatever the counts
+    per_scan = sum((H * W if kind == "HW" else H) * per * (4 if np.dtype(dt) == np.float32 else 8)
+                   for _, dt, kind, per, _ in _abi.ARRAYS)
+    n = max(1, min(DUMP_SLOTS, B, (DUMP_MAX_BYTES - 64 * B - 4096) // per_scan))
+    slots = np.sort(np.random.default_rng(2024).choice(B, size=n, replace=False))
+    res = [pipe.fetch(int(b)) for b in slots]
+    arrays = {"counts": pipe.batch_counts(B), "sample_slots": slots,
+              "scan_counts": np.array([[r[k] for k in _abi.COUNTS] for r in res]),
+              "orientation": np.stack([r["orientation"] for r in res])}
+    for name, *_ in _abi.ARRAYS:
+        arrays[name] = np.concatenate([r[name] for r in res])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def ctypes_sizeof_report() -> int:
     import ctypes
     from llsr import _abi
@@ -851,6 +884,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the per-kernel profiling pass and rooflines, the parity spot "
+                         "check, the CPU baselines and every side leg (the options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--batch", type=int, default=2048, help="scans per GPU per step")
     ap.add_argument("--distinct", type=int, default=16, help="distinct synthetic scans per rank")
     ap.add_argument("--streams", type=int, default=3,
@@ -897,7 +935,7 @@ def main():
         torch.cuda.set_device(0)
     dev = torch.cuda.current_device()
     rccl1 = None  # world 1: a one-rank RCCL group for the configs[4] leg's per-iteration all-reduce
-    if world == 1 and args.allreduce_scans > 0:
+    if world == 1 and args.full and args.allreduce_scans > 0:
         import torch.distributed as rccl1
         rccl1.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{free_port()}", rank=0, world_size=1,
                                  device_id=torch.device("cuda", dev))
@@ -933,6 +971,44 @@ def main():
     if dist:
         dist.barrier()
     el = time.perf_counter() - t0
+    if dist:
+        t = torch.tensor([el], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        el = float(t.item())
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # before any later pass advances a handle's per-slot state past the last timed step
+        dump_outputs(args.dump_outputs, pipes[(args.steps - 1) % nS], B)
+    value = B * args.steps * world / el
+    out = {
+        "metric": "scans/sec (VLP-16 1800x16) at 1/2/4/8 GPUs; pose delta vs CPU ref",
+        "value": round(value, 1),
+        "unit": "scans/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(el / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "build_id": build_id(),
+        "dtype": "fp32",
+        "data": "synthetic (seeded ray-cast VLP-16 street scenes, 2% dropout, 1 cm noise)",
+        "config": {"workload": "configs[1]: VLP-16 1800x16 projection + ground/cluster segmentation "
+                               "+ curvature/feature extraction, labels/indices bit-exact vs CPU",
+                   "lidar": "VLP-16", "rings": H, "columns": W, "scans_per_gpu_per_step": B,
+                   "distinct_clouds_per_gpu": args.distinct, "streams_per_gpu": nS,
+                   "parallelism": f"scan-sharded x{world}"},
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure only (everything below is behind --full)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        for p_ in pipes:
+            p_.close()
+        if dist:
+            dist.destroy_process_group()
+        return
+
     # Per-kernel device times for the roofline: a separate pass of `prof_batches` batches on ONE
     # stream (HIP events recorded on the launch stream between the kernels of each batch), so the
     # other streams' concurrent kernels do not stretch the intervals. Same data, same kernels.
@@ -941,10 +1017,6 @@ def main():
         pipe.process_batch(d_pts.data_ptr(), d_off.data_ptr(), B, streams[0].cuda_stream)
     ktimes = pipe.kernel_times()  # ms per batch
     pipe.set_profiling(False)
-    if dist:
-        t = torch.tensor([el], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        el = float(t.item())
 
     # per-scan counts for the algorithmic-byte model, and a parity spot check of slot 0
     cnt = pipe.batch_counts(B)  # N, S, O, M, sharp, F, L, K
@@ -974,8 +1046,6 @@ def main():
     sel_ms = ktimes["k_select_ring"] + ktimes.get("k_vox_pcl", 0.0)
     dom = max((k for k in ktimes if k not in ("init", "k_vox_pcl")),
               key=lambda k: sel_ms if k == "k_select_ring" else ktimes[k])
-    total_scans = B * args.steps * world
-    value = total_scans / el
     parity = None
     if rank == 0 and not args.no_cpu:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
@@ -1072,25 +1142,7 @@ def main():
                                         rank == 0 and not args.no_cpu)
 
     if rank == 0:
-        out = {
-            "metric": "scans/sec (VLP-16 1800x16) at 1/2/4/8 GPUs; pose delta vs CPU ref",
-            "value": round(value, 1),
-            "unit": "scans/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(el / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "build_id": build_id(),
-            "dtype": "fp32",
-            "data": "synthetic (seeded ray-cast VLP-16 street scenes, 2% dropout, 1 cm noise)",
-            "config": {"workload": "configs[1]: VLP-16 1800x16 projection + ground/cluster segmentation "
-                                   "+ curvature/feature extraction, labels/indices bit-exact vs CPU",
-                       "lidar": "VLP-16", "rings": H, "columns": W, "scans_per_gpu_per_step": B,
-                       "distinct_clouds_per_gpu": args.distinct, "streams_per_gpu": nS,
-                       "parallelism": f"scan-sharded x{world}"},
+        out.update({
             "roofline": roof_dom,
             # north_star's kernel: the (fused) projection + range image + column ground pass
             "roofline_projection": roof_proj,
@@ -1106,7 +1158,7 @@ def main():
             "local_map": lmap,
             "mapping": mapping,
             "pointcloud2_decode": pc2,
-        }
+        })
         if not args.no_cpu and world == 1:
             scans = [pts[off[k]:off[k + 1]] for k in range(min(args.distinct, B))]
             out["cpu_baseline"] = cpu_baseline(scans, args.cpu_seconds)

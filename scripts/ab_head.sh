@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${TAG:-abh}
 mkdir -p "$OUT"
-H="--no-cpu --s2m-modes= --odo= --map-keyframes 0 --pc2 0 --mapping= --allreduce-scans 0 ${BENCH_ARGS:-}"
+H="--full --no-cpu --s2m-modes= --odo= --map-keyframes 0 --pc2 0 --mapping= --allreduce-scans 0 ${BENCH_ARGS:-}"
 if [ -n "${TESTS:-}" ]; then
   timeout -k 10 600 python -u -m pytest $TESTS -v -m gpu -x --timeout 120 --timeout-method thread > "$OUT/pytest.log" 2>&1 || exit $?
 fi

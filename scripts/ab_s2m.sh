@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${TAG:-abs2m}; mkdir -p "$OUT"
-A="--no-cpu --odo= --map-keyframes 0 --pc2 0 --mapping= --allreduce-scans 0 --steps 3 --warmup 1 --batch 512"
+A="--full --no-cpu --odo= --map-keyframes 0 --pc2 0 --mapping= --allreduce-scans 0 --steps 3 --warmup 1 --batch 512"
 for round in 1 2; do
   timeout -k 10 300 python bench.py $A > "$OUT/tree_$round.json" 2>"$OUT/tree_$round.err" || exit $?
   for n in ${LIBS:?}; do

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${TAG:-bsweep}; mkdir -p "$OUT"
-A="--s2m-modes= --odo= --map-keyframes 0 --pc2 0 --mapping= --allreduce-scans 0 --no-cpu --steps 20"
+A="--full --s2m-modes= --odo= --map-keyframes 0 --pc2 0 --mapping= --allreduce-scans 0 --no-cpu --steps 20"
 for b in ${BATCHES:-1024 2048 4096}; do
   for n in ${STREAMS:-3}; do
     timeout -k 10 200 python bench.py $A --batch $b --streams $n > "$OUT/b${b}_s$n.json" 2> "$OUT/b${b}_s$n.err" || exit $?

@@ -15,10 +15,10 @@ step() {  # name timeout cmd...
   return 0
 }
 [ "${SKIP_TESTS:-0}" = 1 ] || step pytest_gpu 900 python -u -m pytest tests -v -m gpu -x --timeout 120 --timeout-method thread
-[ "${SKIP_BENCH:-0}" = 1 ] || step bench 600 python bench.py ${BENCH_ARGS:-}
+[ "${SKIP_BENCH:-0}" = 1 ] || step bench 600 python bench.py --full ${BENCH_ARGS:-}
 if [ "${PROF:-1}" = 1 ]; then
   export TMPDIR=/tmp
-  step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/prof" -o run -- python3 bench.py --steps 5 --warmup 1 --no-cpu
+  step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/prof" -o run -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu
   python3 scripts/trace_prof_pass.py "$OUT/prof/run_kernel_trace.csv" 1 5 3 > "$OUT/prof_pass.json" 2>&1
 fi
 echo done >> "$OUT/steps.log"

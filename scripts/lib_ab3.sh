@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${TAG:-ab3}; mkdir -p "$OUT"
-A="--odo ${ODO_LEGS:-hdl64e:512} --s2m-modes= --map-keyframes 0 --pc2 0 --mapping= --allreduce-scans 0 --no-cpu --steps 10"
+A="--full --odo ${ODO_LEGS:-hdl64e:512} --s2m-modes= --map-keyframes 0 --pc2 0 --mapping= --allreduce-scans 0 --no-cpu --steps 10"
 for round in 1 2; do
   timeout -k 10 300 python bench.py $A > "$OUT/tree_$round.json" 2>/dev/null || exit $?
   for n in ${LIBS:?}; do

@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${TAG:-pmc_lm}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-COMMON="--steps 1 --warmup 1 --no-cpu --streams 1 --batch 64 --prof-batches 1 --s2m-steps 2 --allreduce-scans 0 --map-keyframes 0 --pc2 0 --mapping="
+COMMON="--full --steps 1 --warmup 1 --no-cpu --streams 1 --batch 64 --prof-batches 1 --s2m-steps 2 --allreduce-scans 0 --map-keyframes 0 --pc2 0 --mapping="
 ARGS_A="$COMMON --s2m-modes lm_applied --odo vlp16:1024"
 ARGS_B="$COMMON --s2m-modes= --odo hdl64e:512"
 SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_LDS"

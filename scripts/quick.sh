@@ -21,7 +21,7 @@ if [ -n "${PHASES:-}" ]; then
   PHASES=$PHASES step phase 300 python -u scripts/phase_profile.py ${PHASE_LIDAR:-vlp16} ${PHASE_B:-1024}
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  step bench 600 python -u bench.py --no-cpu --s2m-modes "" --odo "" --map-keyframes 0 --pc2 0 --mapping "" \
+  step bench 600 python -u bench.py --full --no-cpu --s2m-modes "" --odo "" --map-keyframes 0 --pc2 0 --mapping "" \
     --allreduce-scans 0 ${BENCH_ARGS:-}
 fi
 if [ -n "${EXTRA:-}" ]; then
