@@ -364,7 +364,8 @@ int32_t llsr_scan2map(llsr_handle* h, const float* corner_q, int32_t n_corner_q,
  * scan runs checkSystemInitialization (FA:2291-2315) instead. transformCur carries over to the
  * next scan as the LM's initial guess. Requires LLSR_MODE_LM_APPLIED (LLSR_ENOSYS otherwise): in
  * the faithful mode updateInitialGuess (FA:2790) overwrites transformCur from the /odom2 topic,
- * which has no input here. One host sync per call (the feature counts size the packed clouds). */
+ * which has no input here (llsr_odometry_batch_odom below takes it). One host sync per call (the
+ * feature counts size the packed clouds). */
 typedef struct llsr_odom_slot {
   int32_t frames;            /* scans this slot has consumed */
   int32_t n_corner_last;     /* laserCloudCornerLastNum after the last scan */
@@ -479,8 +480,8 @@ int32_t llsr_map_keyframe_ids(const llsr_map* m, int32_t* out, int32_t cap);
  * saveKeyFramesAndFactor (MO:1612-1755; every frame is a keyframe there, saveThisKeyFrame is forced
  * true at MO:1629; the prior / between factors with the initial values as measurements leave
  * iSAM2's estimate at the initial values, so the key pose is transformTobeMapped for the first
- * keyframe and transformAftMapped after). Requires the handle's mode LLSR_MODE_LM_APPLIED
- * (the odometry's); `mo_mode` selects MapOptimization's own LM mode (LLSR_MODE_FAITHFUL: the pose
+ * keyframe and transformAftMapped after). llsr_mapping_batch requires the handle's mode
+ * LLSR_MODE_LM_APPLIED (the odometry's; llsr_mapping_batch_odom runs either); `mo_mode` selects MapOptimization's own LM mode (LLSR_MODE_FAITHFUL: the pose
  * update at MO:1539-1545 stays commented out, as in the reference). map_cfg NULL selects the
  * config block of the handle's lidar (llsr_map_config_lidar: HDL-64E when num_vertical_scans is
  * 64, else VLP-16), which decides the local-map branch (enable_loop_closure). Synchronises per
@@ -570,6 +571,57 @@ int32_t llsr_fusion_laser_odometry(llsr_fusion_state* st, const llsr_odometry_ms
 /* TransformFusion::odomAftMappedHandler (TF:282-304): transform_aft_mapped from the pose (getRPY
  * of Quaternion(o.z, -o.x, -o.y, o.w) -> -pitch, -yaw, roll), transform_bef_mapped from the twist. */
 int32_t llsr_fusion_aft_mapped(llsr_fusion_state* st, const llsr_odometry_msg* odom_aft_mapped);
+
+/* ---- /odom2 and updateInitialGuess (featureAssociation.cpp:354-383, 2337-2402) ----
+ * After every scan-to-scan LM the reference runs updateInitialGuess (FA:2790), which rebuilds all
+ * six entries of transformCur from the latest /odom2 sample and the previous transformSum; the
+ * rebuilt value is what integrateTransformation, publishCloudsLast and the next LM's initial guess
+ * see. Host side of the library (no device, no handle), double arithmetic in the order the
+ * reference's x86-64 build evaluates Eigen 3.3.7's expressions (glibc sincos /
+ * atan2 / sqrt in double).
+ * llsr_odom_sample holds odomRoll / Pitch / Yaw / PosX / PosY / PosZ[odomPointerLast]; llsr_odom_state
+ * holds odomCallback's members: odomInitialIter, the number of messages seen, x/y/z_initial and the
+ * latest sample (the reference's 200-entry ring is only read at odomPointerLast). */
+typedef struct llsr_odom_sample { float roll, pitch, yaw, x, y, z; } llsr_odom_sample;
+typedef struct llsr_odom_state {
+  int32_t initial_iter;
+  int32_t n_msgs;
+  double origin[3];
+  llsr_odom_sample last;
+} llsr_odom_state;
+/* The constructor's zeros (FA:277-287). `last` is the zero sample: this library's definition of "no
+ * /odom2 message yet", where the reference reads its arrays at index -1. */
+int32_t llsr_odom_init(llsr_odom_state* st);
+/* odomCallback (FA:354-383): tf2 getRPY of the orientation (x, y, z, w as they come) in double,
+ * narrowed to float; the first message latches the origin; position = (double)position - origin,
+ * narrowed to float. Reads orientation and position of the message only. */
+int32_t llsr_odom_callback(llsr_odom_state* st, const llsr_odometry_msg* msg);
+/* updateInitialGuess (FA:2370-2402): reads transform_sum, overwrites all six entries of
+ * transform_cur. */
+int32_t llsr_update_initial_guess(const llsr_odom_sample* sample, const float transform_sum[6],
+                                  float transform_cur[6]);
+
+/* llsr_odometry_batch with updateInitialGuess in program order (FA:2789-2796), accepted in both
+ * handle modes (the FA LM is always applied; llsr_config.mode only ever meant MapOptimization's
+ * update). samples: host [B], the slots' latest /odom2 samples (llsr_odom_state.last); overwrite:
+ * host [B] flags, NULL = every slot. For a slot with overwrite[b] != 0, on every scan after its
+ * first: the LM starts from the slot's carried transformCur; transformCur is then replaced by
+ * llsr_update_initial_guess(samples[b], transformSum); integrateTransformation and the four
+ * TransformToEnd use the replaced value, and it carries over as the next LM's initial guess. The
+ * slot's first scan runs checkSystemInitialization only (the `continue` at FA:2781-2784). A slot
+ * with overwrite[b] == 0 behaves exactly as under llsr_odometry_batch. llsr_odometry_fetch then
+ * reports the replaced transformCur (as the reference's member would read) and `lm` the LM that ran;
+ * llsr_odometry_fetch_lm returns the LM's own transformCur of slot b's last scan (zeros before the
+ * slot's second scan or when the slot was not flagged). Same single host sync as
+ * llsr_odometry_batch: transformSum rides on the feature-count copy, the guesses are evaluated on
+ * the host and uploaded asynchronously. */
+int32_t llsr_odometry_batch_odom(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                                 const llsr_odom_sample* samples, const uint8_t* overwrite, void* hip_stream);
+int32_t llsr_odometry_fetch_lm(llsr_handle* h, int32_t b, float transform_lm[6]);
+/* llsr_mapping_batch over llsr_odometry_batch_odom: same trailing arguments, accepted in both handle
+ * modes (llsr_mapping_init likewise), same rollback contract. */
+int32_t llsr_mapping_batch_odom(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                                const llsr_odom_sample* samples, const uint8_t* overwrite, void* hip_stream);
 
 /* ---- Input wire formats (llsr_input.hip) ----
  * sensor_msgs/PointCloud2 (PointField datatype codes, sensor_msgs/msg/PointField.msg) decoded as

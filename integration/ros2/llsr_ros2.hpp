@@ -9,7 +9,10 @@
 //   FeatureAssociation feature stage         featureAssociation.cpp:2769-2775 (+ 1310-1314 shadow points)
 //                                            -> Projection::handoff (on the IP thread, into ProjectionOut)
 //   runFeatureAssociation after the features featureAssociation.cpp:2777-2796, 2291-2315, 2660-2712
-//                                            -> Odometry::step (on the FA thread, its own handle)
+//                                            -> Odometry::solve / OdomInput::apply / Odometry::finish
+//                                               (on the FA thread, its own handle; step = solve + finish)
+//   FeatureAssociation::odomCallback         featureAssociation.cpp:354-383 -> OdomInput::on_message
+//   FeatureAssociation::updateInitialGuess   featureAssociation.cpp:2337-2402 -> OdomInput::apply
 //   FeatureAssociation::updateTransformation featureAssociation.cpp:2505-2535 -> update_transformation
 //   MapOptimization::scan2MapOptimization    mapOptmization.cpp:1572-1610 -> scan2map_optimization
 //
@@ -24,6 +27,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -328,8 +332,10 @@ llsr_s2s_report update_transformation(llsr_handle* h, const Cloud& corner_sharp,
 // then updateTransformation (FA:2505-2535), integrateTransformation (FA:2537-2568) and
 // publishCloudsLast (FA:2660-2712: TransformToEnd of the less-sharp / less-flat clouds, which
 // become the last clouds + the shadow points, and of the sharp / flat clouds, MO's scan clouds).
-// updateInitialGuess (FA:2790) and publishOdometry stay node code; without an IMU, transformCur
-// carries over as the next LM's initial guess (LLSR_MODE_LM_APPLIED semantics).
+// The reference's order (FA:2781-2796) is solve(f), then OdomInput::apply(transform_sum,
+// transform_cur) for updateInitialGuess (FA:2790), then finish(f), then the node's publishOdometry;
+// step(f) = solve + finish leaves the LM's transformCur in place (LLSR_MODE_LM_APPLIED semantics).
+// Either way transform_cur carries over as the next LM's initial guess.
 template <class Cloud>
 class Odometry {
  public:
@@ -339,8 +345,10 @@ class Odometry {
   }
   llsr_handle* handle() const { return h_.get(); }
 
-  // one scan's features (moved from the channel's ProjectionOut); false on the initialisation scan
-  bool step(FeatureClouds<Cloud>& f) {
+  // one scan's features (moved from the channel's ProjectionOut): checkSystemInitialization on the
+  // first scan (returns false: the `continue` at FA:2781-2784, finish must not follow), else
+  // updateTransformation (FA:2789)
+  bool solve(FeatureClouds<Cloud>& f) {
     if (!inited_) {
       corner_last = std::move(f.corner_less_sharp);
       surf_last = std::move(f.surf_less_flat);
@@ -350,12 +358,22 @@ class Odometry {
     }
     report = update_transformation(h_.get(), f.corner_sharp, f.surf_flat, corner_last, surf_last, transform_cur,
                                    is_degenerate);
+    return true;
+  }
+  // integrateTransformation and publishCloudsLast's four TransformToEnd (FA:2792-2796) with whatever
+  // transform_cur then holds
+  void finish(FeatureClouds<Cloud>& f) {
     check(llsr_integrate_transformation(transform_sum, transform_cur), nullptr, "llsr_integrate_transformation");
     transform_to_end(transform_cur, f.corner_less_sharp, corner_last);
     transform_to_end(transform_cur, f.surf_less_flat, surf_last);
     append_xyzi(shadow_.data(), (int32_t)(shadow_.size() / 4), surf_last);
     transform_to_end(transform_cur, f.corner_sharp, corner_scan);
     transform_to_end(transform_cur, f.surf_flat, surf_scan);
+  }
+  // solve then finish; false on the initialisation scan
+  bool step(FeatureClouds<Cloud>& f) {
+    if (!solve(f)) return false;
+    finish(f);
     return true;
   }
 
@@ -371,6 +389,44 @@ class Odometry {
   Handle h_;
   bool inited_ = false;
   std::vector<float> shadow_;
+};
+
+// FeatureAssociation's /odom2 members (FA:277-287) behind a mutex: the subscription's callback runs
+// on another thread than runFeatureAssociation. on_message is odomCallback (FA:354-383) for any
+// message type with nav_msgs/Odometry's pose.pose.orientation / position fields; apply is
+// updateInitialGuess (FA:2370-2402) with the latest sample (the zero sample before any message).
+class OdomInput {
+ public:
+  OdomInput() { check(llsr_odom_init(&st_), nullptr, "llsr_odom_init"); }
+  template <class Msg>
+  void on_message(const Msg& msg) {
+    llsr_odometry_msg m = llsr_odometry_msg();
+    m.orientation[0] = msg.pose.pose.orientation.x;
+    m.orientation[1] = msg.pose.pose.orientation.y;
+    m.orientation[2] = msg.pose.pose.orientation.z;
+    m.orientation[3] = msg.pose.pose.orientation.w;
+    m.position[0] = msg.pose.pose.position.x;
+    m.position[1] = msg.pose.pose.position.y;
+    m.position[2] = msg.pose.pose.position.z;
+    std::lock_guard<std::mutex> lk(m_);
+    check(llsr_odom_callback(&st_, &m), nullptr, "llsr_odom_callback");
+  }
+  llsr_odom_sample sample() const {
+    std::lock_guard<std::mutex> lk(m_);
+    return st_.last;
+  }
+  int32_t messages() const {
+    std::lock_guard<std::mutex> lk(m_);
+    return st_.n_msgs;
+  }
+  void apply(const float transform_sum[6], float transform_cur[6]) const {
+    const llsr_odom_sample s = sample();
+    check(llsr_update_initial_guess(&s, transform_sum, transform_cur), nullptr, "llsr_update_initial_guess");
+  }
+
+ private:
+  mutable std::mutex m_;
+  llsr_odom_state st_;
 };
 
 // scan2MapOptimization (MO:1572-1610) once its guard (MO:1573: corner map > 10, surf map > 100)

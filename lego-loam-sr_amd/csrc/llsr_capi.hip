@@ -20,6 +20,7 @@
 #include "llsr_mapping.h"
 #include "llsr_mo.h"
 #include "llsr_odo.h"
+#include "llsr_odom_guess.h"
 #include "llsr_s2s.h"
 
 namespace llsr {
@@ -134,6 +135,14 @@ struct llsr_handle {
     int64_t* h_off = nullptr;     // pinned host copy
     int* h_counts = nullptr;      // pinned [B][kCnt]
     llsr_s2s_report* report = nullptr;  // [B]
+    // llsr_odometry_batch_odom: updateInitialGuess's transformCur per slot, the slots it replaces
+    // the LM's in, and the LM's own result of those slots
+    float* guess = nullptr;       // [B][6]
+    float* tlm = nullptr;         // [B][6]
+    unsigned char* flags = nullptr;  // [B]
+    float* h_tsum = nullptr;      // pinned [B][6] transformSum, then h_guess [B][6] and h_flags [B]
+    float* h_guess = nullptr;
+    unsigned char* h_flags = nullptr;
     int cur = 0;                  // last_c/s[cur] hold the current last clouds
   } odo;
   // mapping chain (llsr_mapping_*): MapOptimization's members per slot + the batch buffers
@@ -428,6 +437,7 @@ extern "C" void llsr_destroy(llsr_handle* h) {
   if (h->odo.pool) (void)hipFree(h->odo.pool);
   if (h->odo.h_off) (void)hipHostFree(h->odo.h_off);
   if (h->odo.h_counts) (void)hipHostFree(h->odo.h_counts);
+  if (h->odo.h_tsum) (void)hipHostFree(h->odo.h_tsum);
   if (h->mo.stage) (void)hipFree(h->mo.stage);
   if (h->mo.host_flags) (void)hipHostFree(h->mo.host_flags);
   if (h->mo.e0) (void)hipEventDestroy(h->mo.e0);
@@ -1538,9 +1548,9 @@ static int32_t odo_alloc(llsr_handle* h) {
   const size_t per = (size_t)h->dc.HW + kShadow;
   o.B = B;
   o.cap = (size_t)B * per;
-  const size_t bytes = sizeof(float) * 12 * B + sizeof(int) * 3 * B + sizeof(float4) * kShadow +
+  const size_t bytes = sizeof(float) * 24 * B + B + sizeof(int) * 3 * B + sizeof(float4) * kShadow +
                        sizeof(float4) * 8 * o.cap + sizeof(int64_t) * 6 * (B + 1) + sizeof(llsr_s2s_report) * B +
-                       16 * 256;
+                       24 * 256;
   if (hipMalloc(&o.pool, bytes) != hipSuccess) {
     o.pool = nullptr;
     return fail(h, LLSR_ENOMEM, "odometry buffers");
@@ -1562,9 +1572,15 @@ static int32_t odo_alloc(llsr_handle* h) {
   }
   o.off = carve<int64_t>(q, 6 * (size_t)(B + 1));
   o.report = carve<llsr_s2s_report>(q, B);
+  o.guess = carve<float>(q, 6 * (size_t)B);
+  o.tlm = carve<float>(q, 6 * (size_t)B);
+  o.flags = carve<unsigned char>(q, B);
   if (hipHostMalloc((void**)&o.h_off, sizeof(int64_t) * 6 * (B + 1)) != hipSuccess ||
-      hipHostMalloc((void**)&o.h_counts, sizeof(int) * kCnt * B) != hipSuccess)
+      hipHostMalloc((void**)&o.h_counts, sizeof(int) * kCnt * B) != hipSuccess ||
+      hipHostMalloc((void**)&o.h_tsum, sizeof(float) * 12 * B + B) != hipSuccess)
     return fail(h, LLSR_ENOMEM, "pinned odometry staging");
+  o.h_guess = o.h_tsum + 6 * (size_t)B;
+  o.h_flags = (unsigned char*)(o.h_guess + 6 * (size_t)B);
   float sh[4 * kShadow];
   llsr_shadow_points(sh);
   HIP_OK(h, hipMemcpy(o.shadow, sh, sizeof sh, hipMemcpyHostToDevice));
@@ -1585,17 +1601,19 @@ extern "C" int32_t llsr_odometry_reset(llsr_handle* h) {
   HIP_OK(h, hipMemset(o.frames, 0, sizeof(int) * B));
   HIP_OK(h, hipMemset(o.off, 0, sizeof(int64_t) * 6 * (B + 1)));
   HIP_OK(h, hipMemset(o.report, 0, sizeof(llsr_s2s_report) * B));
+  HIP_OK(h, hipMemset(o.guess, 0, sizeof(float) * 6 * B));
+  HIP_OK(h, hipMemset(o.tlm, 0, sizeof(float) * 6 * B));
+  HIP_OK(h, hipMemset(o.flags, 0, B));
   std::memset(o.h_off, 0, sizeof(int64_t) * 6 * (B + 1));
   o.cur = 0;
   return LLSR_OK;
 }
 
-extern "C" int32_t llsr_odometry_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
-                                       void* hip_stream) {
-  if (!h) return LLSR_EINVAL;
-  if (h->cfg.mode != LLSR_MODE_LM_APPLIED)
-    return fail(h, LLSR_ENOSYS, "odometry needs LLSR_MODE_LM_APPLIED: faithful mode overwrites transformCur "
-                                "from the /odom2 topic (updateInitialGuess, FA:2790), which has no input here");
+// llsr_odometry_batch (samples == nullptr) and llsr_odometry_batch_odom: with samples, transformSum
+// rides on the feature-count copy, updateInitialGuess (FA:2790) is evaluated on the host for the
+// flagged slots and k_odo_finish swaps it in after the LM.
+static int32_t odo_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                         const llsr_odom_sample* samples, const uint8_t* overwrite, void* hip_stream) {
   if (B < 1 || B > h->max_batch) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
   HIP_OK(h, hipSetDevice(h->device));
   int32_t rc = odo_alloc(h);
@@ -1606,6 +1624,9 @@ extern "C" int32_t llsr_odometry_batch(llsr_handle* h, const float* d_xyzi, cons
   if (rc != LLSR_OK) return rc;
   // the feature counts size the packed clouds: one host sync per batch
   HIP_OK(h, hipMemcpyAsync(o.h_counts, h->d.counts, sizeof(int) * kCnt * B, hipMemcpyDeviceToHost, s));
+  // the transformSum updateInitialGuess reads is the previous frame's: it does not depend on this
+  // frame's LM, and llsr_process_batch ordered s after the previous call's k_odo_finish (last_done)
+  if (samples) HIP_OK(h, hipMemcpyAsync(o.h_tsum, o.tsum, sizeof(float) * 6 * B, hipMemcpyDeviceToHost, s));
   HIP_OK(h, hipStreamSynchronize(s));
   const int nb = o.B + 1;
   int64_t* hs = o.h_off;                       // sharp
@@ -1656,6 +1677,7 @@ extern "C" int32_t llsr_odometry_batch(llsr_handle* h, const float* d_xyzi, cons
   a.nlast_s_off = o.off + (4 + nxt) * nb; a.nlast_s = o.last_s[nxt];
   a.scan_c = o.scan_c; a.scan_s = o.scan_s;
   a.tcur = o.tcur; a.tsum = o.tsum; a.inited = o.inited; a.frames = o.frames;
+  if (samples) { a.guess = o.guess; a.flags = o.flags; a.tlm = o.tlm; }
   k_odo_inputs<<<B, 256, 0, s>>>(a);
   HIP_OK(h, hipGetLastError());
   llsr_s2s_batch sb{};
@@ -1670,12 +1692,50 @@ extern "C" int32_t llsr_odometry_batch(llsr_handle* h, const float* d_xyzi, cons
   // the LM instantiation follows this batch's clouds, not the (high-water) reserve
   rc = s2s_launch(h, &sb, s, std::max(std::max(mMs, mF), 1), std::max(mNc, 1));
   if (rc != LLSR_OK) return rc;
+  if (samples) {  // evaluated while the LM runs: only k_odo_finish reads the guesses
+    for (int b = 0; b < B; ++b) {
+      o.h_flags[b] = overwrite ? (overwrite[b] != 0) : 1;
+      if (o.h_flags[b]) llsr_odom::update_initial_guess(samples[b], o.h_tsum + 6 * b, o.h_guess + 6 * b);
+      else std::memset(o.h_guess + 6 * b, 0, sizeof(float) * 6);
+    }
+    HIP_OK(h, hipMemcpyAsync(o.guess, o.h_guess, sizeof(float) * 6 * B, hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(o.flags, o.h_flags, B, hipMemcpyHostToDevice, s));
+  }
   k_odo_finish<<<B, 256, 0, s>>>(a);
   HIP_OK(h, hipGetLastError());
   HIP_OK(h, hipEventRecord(h->last_done, s));
   h->last_rec = true;
   o.cur = nxt;
   h->last_stream = s;
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_odometry_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                                       void* hip_stream) {
+  if (!h) return LLSR_EINVAL;
+  if (h->cfg.mode != LLSR_MODE_LM_APPLIED)
+    return fail(h, LLSR_ENOSYS, "odometry needs LLSR_MODE_LM_APPLIED: faithful mode overwrites transformCur "
+                                "from the /odom2 topic (updateInitialGuess, FA:2790), which has no input here "
+                                "(llsr_odometry_batch_odom takes it)");
+  return odo_batch(h, d_xyzi, d_offsets, B, nullptr, nullptr, hip_stream);
+}
+
+extern "C" int32_t llsr_odometry_batch_odom(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                                            const llsr_odom_sample* samples, const uint8_t* overwrite,
+                                            void* hip_stream) {
+  if (!h) return LLSR_EINVAL;
+  if (!samples) return fail(h, LLSR_EINVAL, "llsr_odometry_batch_odom: samples is NULL");
+  return odo_batch(h, d_xyzi, d_offsets, B, samples, overwrite, hip_stream);
+}
+
+extern "C" int32_t llsr_odometry_fetch_lm(llsr_handle* h, int32_t b, float* transform_lm) {
+  if (!h || !transform_lm) return LLSR_EINVAL;
+  auto& o = h->odo;
+  if (!o.pool) return fail(h, LLSR_EINVAL, "llsr_odometry_batch not called");
+  if (b < 0 || b >= o.B) return fail(h, LLSR_ERANGE, "slot outside [0, max_batch)");
+  int32_t rc = sync_last(h);
+  if (rc) return rc;
+  HIP_OK(h, d2h(transform_lm, o.tlm + 6 * b, 6));
   return LLSR_OK;
 }
 
@@ -1780,8 +1840,7 @@ static void mapping_free(llsr_handle* h) {
 extern "C" int32_t llsr_mapping_init(llsr_handle* h, int32_t mo_mode, const llsr_map_config* map_cfg) {
   if (!h) return LLSR_EINVAL;
   if (mo_mode != LLSR_MODE_FAITHFUL && mo_mode != LLSR_MODE_LM_APPLIED) return fail(h, LLSR_EINVAL, "mo_mode");
-  if (h->cfg.mode != LLSR_MODE_LM_APPLIED)
-    return fail(h, LLSR_ENOSYS, "the mapping chain runs the odometry, which needs LLSR_MODE_LM_APPLIED");
+  // both handle modes: llsr_mapping_batch refuses the faithful one itself, llsr_mapping_batch_odom runs it
   llsr_map_config mcfg;
   if (map_cfg) mcfg = *map_cfg;  // NULL: the YAML block of the handle's lidar
   else llsr_map_config_lidar(&mcfg, h->dc.H == 64 ? LLSR_LIDAR_HDL64E : LLSR_LIDAR_VLP16);
@@ -2011,15 +2070,15 @@ static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::v
   return LLSR_OK;
 }
 
-extern "C" int32_t llsr_mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
-                                      void* hip_stream) {
-  if (!h) return LLSR_EINVAL;
+// llsr_mapping_batch (samples == nullptr) and llsr_mapping_batch_odom
+static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                             const llsr_odom_sample* samples, const uint8_t* overwrite, void* hip_stream) {
   auto& mp = h->mp;
   if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
   if (B < 1 || B > h->max_batch) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
   HIP_OK(h, hipSetDevice(h->device));
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  int32_t rc = llsr_odometry_batch(h, d_xyzi, d_offsets, B, s);
+  int32_t rc = odo_batch(h, d_xyzi, d_offsets, B, samples, overwrite, s);
   if (rc != LLSR_OK) return rc;
   auto& o = h->odo;
   HIP_OK(h, hipMemcpyAsync(mp.h_frames, o.frames, sizeof(int) * B, hipMemcpyDeviceToHost, s));
@@ -2089,6 +2148,23 @@ extern "C" int32_t llsr_mapping_batch(llsr_handle* h, const float* d_xyzi, const
   h->last_rec = true;
   h->last_stream = s;
   return LLSR_OK;
+}
+
+extern "C" int32_t llsr_mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                                      void* hip_stream) {
+  if (!h) return LLSR_EINVAL;
+  if (h->cfg.mode != LLSR_MODE_LM_APPLIED)
+    return fail(h, LLSR_ENOSYS, "the mapping chain runs the odometry, which needs LLSR_MODE_LM_APPLIED "
+                                "(llsr_mapping_batch_odom takes the /odom2 input of the faithful mode)");
+  return mapping_batch(h, d_xyzi, d_offsets, B, nullptr, nullptr, hip_stream);
+}
+
+extern "C" int32_t llsr_mapping_batch_odom(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                                           const llsr_odom_sample* samples, const uint8_t* overwrite,
+                                           void* hip_stream) {
+  if (!h) return LLSR_EINVAL;
+  if (!samples) return fail(h, LLSR_EINVAL, "llsr_mapping_batch_odom: samples is NULL");
+  return mapping_batch(h, d_xyzi, d_offsets, B, samples, overwrite, hip_stream);
 }
 
 extern "C" int32_t llsr_mapping_fetch(llsr_handle* h, int32_t b, llsr_mapping_slot* out) {
@@ -2226,5 +2302,27 @@ extern "C" int32_t llsr_transform_to_end(const float* transform_cur, const float
     o[2] = q.z;
     o[3] = q.w;
   }
+  return LLSR_OK;
+}
+
+// ---- /odom2 and updateInitialGuess (FA:354-383, 2337-2402): host-side scalar glue, llsr_odom_guess.h
+extern "C" int32_t llsr_odom_init(llsr_odom_state* st) {
+  if (!st) return LLSR_EINVAL;
+  std::memset(st, 0, sizeof *st);  // FA:277-287; `last` = the zero sample ("no message yet")
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_odom_callback(llsr_odom_state* st, const llsr_odometry_msg* msg) {
+  if (!st || !msg) return LLSR_EINVAL;
+  llsr_odom::callback(*st, *msg);
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_update_initial_guess(const llsr_odom_sample* sample, const float* transform_sum,
+                                             float* transform_cur) {
+  if (!sample || !transform_sum || !transform_cur) return LLSR_EINVAL;
+  float ts[6];
+  for (int k = 0; k < 6; ++k) ts[k] = transform_sum[k];  // transform_cur may alias transform_sum
+  llsr_odom::update_initial_guess(*sample, ts, transform_cur);
   return LLSR_OK;
 }

@@ -29,6 +29,10 @@ struct OdoArgs {
   float* tsum;                             // [B][6] transformSum
   int* inited;                             // [B] systemInitedLM
   int* frames;                             // [B]
+  // updateInitialGuess after the LM (FA:2790, llsr_odometry_batch_odom); all nullptr otherwise
+  const float* guess;                      // [B][6] the transformCur it builds (host-evaluated)
+  const unsigned char* flags;              // [B] slots whose transformCur it replaces
+  float* tlm;                              // [B][6] the LM's own transformCur of those slots
 };
 
 __global__ void k_odo_inputs(OdoArgs a);

@@ -44,7 +44,8 @@ EXPORTS = [
     "llsr_mapping_init", "llsr_mapping_batch", "llsr_mapping_fetch", "llsr_mapping_keyposes", "llsr_mapping_reset",
     "llsr_mapping_associate", "llsr_set_voxel_order", "llsr_scan2scan_stats", "llsr_fusion_init",
     "llsr_pose_to_odometry", "llsr_odometry_to_transform", "llsr_fusion_laser_odometry", "llsr_fusion_aft_mapped",
-    "llsr_integrate_transformation", "llsr_transform_to_end",
+    "llsr_integrate_transformation", "llsr_transform_to_end", "llsr_odom_init", "llsr_odom_callback",
+    "llsr_update_initial_guess", "llsr_odometry_batch_odom", "llsr_odometry_fetch_lm", "llsr_mapping_batch_odom",
 ]
 
 
@@ -116,6 +117,13 @@ def lib():
         L.llsr_odometry_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.llsr_odometry_fetch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.OdomSlot)] + [C.c_void_p] * 4
         L.llsr_odometry_reset.argtypes = [C.c_void_p]
+        L.llsr_odometry_batch_odom.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+        L.llsr_odometry_fetch_lm.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.llsr_mapping_batch_odom.argtypes = L.llsr_odometry_batch_odom.argtypes
+        L.llsr_odom_init.argtypes = [C.POINTER(_abi.OdomState)]
+        L.llsr_odom_callback.argtypes = [C.POINTER(_abi.OdomState), C.POINTER(_abi.OdometryMsg)]
+        L.llsr_update_initial_guess.argtypes = [C.POINTER(_abi.OdomSample), C.c_void_p, C.c_void_p]
         L.llsr_map_config_default.argtypes = [C.POINTER(_abi.MapConfig)]
         L.llsr_map_config_lidar.argtypes = [C.POINTER(_abi.MapConfig), C.c_int32]
         L.llsr_map_create.argtypes = [C.POINTER(_abi.MapConfig), C.c_int32]
@@ -372,6 +380,33 @@ class Pipeline:
                 d[name] = a[:n].copy()
         return d
 
+    @staticmethod
+    def _odom_args(samples, overwrite, B: int):
+        """samples: B sequences of roll, pitch, yaw, x, y, z (or _abi.OdomSample); overwrite: B flags or None."""
+        if isinstance(samples, C.Array) and samples._type_ is _abi.OdomSample and len(samples) >= B:
+            arr = samples  # a caller-built llsr_odom_sample[B] goes through as it is
+        else:
+            arr = (_abi.OdomSample * B)()
+            for b in range(B):
+                v = samples[b]
+                arr[b] = v if isinstance(v, _abi.OdomSample) else _abi.OdomSample(*(float(x) for x in v))
+        flags = None if overwrite is None else np.ascontiguousarray(overwrite, np.uint8).reshape(B)
+        return arr, flags
+
+    def odometry_batch_odom(self, d_xyzi: int, d_offsets: int, B: int, samples, overwrite=None, stream: int = 0):
+        """odometry_batch with updateInitialGuess after the LM (FA:2790): samples[b] is slot b's latest
+        /odom2 sample, overwrite[b] selects the slots it applies to (None: every slot)."""
+        arr, flags = self._odom_args(samples, overwrite, B)
+        self._check(lib().llsr_odometry_batch_odom(self._h, C.c_void_p(d_xyzi), C.c_void_p(d_offsets), B, arr,
+                                                   None if flags is None else flags.ctypes.data,
+                                                   C.c_void_p(stream)), "llsr_odometry_batch_odom")
+
+    def odometry_fetch_lm(self, b: int) -> np.ndarray:
+        """The LM's own transformCur of slot b's last scan (before updateInitialGuess replaced it)."""
+        out = np.zeros(6, np.float32)
+        self._check(lib().llsr_odometry_fetch_lm(self._h, b, out.ctypes.data), "llsr_odometry_fetch_lm")
+        return out
+
     def odometry_reset(self):
         self._check(lib().llsr_odometry_reset(self._h), "llsr_odometry_reset")
 
@@ -385,6 +420,13 @@ class Pipeline:
         """One device-resident scan per slot through IP + FA + odometry + MapOptimization."""
         self._check(lib().llsr_mapping_batch(self._h, C.c_void_p(d_xyzi), C.c_void_p(d_offsets), B,
                                              C.c_void_p(stream)), "llsr_mapping_batch")
+
+    def mapping_batch_odom(self, d_xyzi: int, d_offsets: int, B: int, samples, overwrite=None, stream: int = 0):
+        """mapping_batch over odometry_batch_odom (same samples / overwrite arguments)."""
+        arr, flags = self._odom_args(samples, overwrite, B)
+        self._check(lib().llsr_mapping_batch_odom(self._h, C.c_void_p(d_xyzi), C.c_void_p(d_offsets), B, arr,
+                                                  None if flags is None else flags.ctypes.data,
+                                                  C.c_void_p(stream)), "llsr_mapping_batch_odom")
 
     def mapping_fetch(self, b: int) -> dict:
         st = _abi.MappingSlot()
@@ -484,6 +526,39 @@ class TransformFusion:
         """transformSum, transformIncre, transformMapped, transformBefMapped, transformAftMapped."""
         st = self.state
         return np.concatenate([np.array(getattr(st, f), np.float32) for f, _ in st._fields_])
+
+
+def odom_init() -> "_abi.OdomState":
+    """llsr_odom_init: FeatureAssociation's /odom2 members before any message (the zero sample)."""
+    st = _abi.OdomState()
+    rc = lib().llsr_odom_init(C.byref(st))
+    if rc != 0:
+        raise LlsrError(f"llsr_odom_init: {rc}")
+    return st
+
+
+def odom_callback(state: "_abi.OdomState", msg) -> np.ndarray:
+    """odomCallback (FA:354-383) of a 13-double odometry message (orientation xyzw, position, twist;
+    7 doubles are enough); updates `state` and returns its latest sample roll, pitch, yaw, x, y, z."""
+    a = np.zeros(13, np.float64)
+    m = np.asarray(msg, np.float64).reshape(-1)
+    a[:len(m)] = m
+    rc = lib().llsr_odom_callback(C.byref(state), C.byref(_array_to_msg(a)))
+    if rc != 0:
+        raise LlsrError(f"llsr_odom_callback: {rc}")
+    return state.last.as_array()
+
+
+def update_initial_guess(sample, transform_sum) -> np.ndarray:
+    """updateInitialGuess (FA:2370-2402): the transformCur it builds from the /odom2 sample (roll,
+    pitch, yaw, x, y, z or _abi.OdomSample) and transformSum."""
+    smp = sample if isinstance(sample, _abi.OdomSample) else _abi.OdomSample(*(float(x) for x in sample))
+    ts = np.ascontiguousarray(transform_sum, np.float32).reshape(6)
+    out = np.zeros(6, np.float32)
+    rc = lib().llsr_update_initial_guess(C.byref(smp), ts.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise LlsrError(f"llsr_update_initial_guess: {rc}")
+    return out
 
 
 def shadow_points() -> np.ndarray:

@@ -227,6 +227,22 @@ class OdometryMsg(C.Structure):
                 ("twist_angular", C.c_double * 3), ("twist_linear", C.c_double * 3)]
 
 
+class OdomSample(C.Structure):
+    """llsr_odom_sample: odomRoll / Pitch / Yaw / PosX / PosY / PosZ[odomPointerLast]."""
+    _fields_ = [("roll", C.c_float), ("pitch", C.c_float), ("yaw", C.c_float),
+                ("x", C.c_float), ("y", C.c_float), ("z", C.c_float)]
+
+    def as_array(self):
+        import numpy as np
+        return np.array([self.roll, self.pitch, self.yaw, self.x, self.y, self.z], np.float32)
+
+
+class OdomState(C.Structure):
+    """llsr_odom_state: odomCallback's members (FA:354-383)."""
+    _fields_ = [("initial_iter", C.c_int32), ("n_msgs", C.c_int32), ("origin", C.c_double * 3),
+                ("last", OdomSample)]
+
+
 class FusionState(C.Structure):
     """llsr_fusion_state: TransformFusion's members (transformFusion.h)."""
     _fields_ = [("transform_sum", C.c_float * 6), ("transform_incre", C.c_float * 6),

@@ -189,6 +189,24 @@ def make_scan(seed: int, lidar: str = VLP16, dropout: float = 0.02, noise: float
     return pts
 
 
+def odom_message(seed: int) -> np.ndarray:
+    """The /odom2 message (nav_msgs/Odometry) for frame `seed` of its drive, as the 13 doubles of
+    llsr_odometry_msg (orientation x, y, z, w; position; twist zeros), from the ground truth
+    `make_scan(seed, motion=True)` uses: position (0.5 * (seed % 64), the scan's y draw, dz) and the
+    attitude `_rot_zyx(roll, pitch, yaw)` of `sensor_attitude(seed)` as a quaternion. Deterministic,
+    and it varies in all six degrees of freedom; it does not model the reference's lever arm."""
+    dz, roll, pitch, yaw = sensor_attitude(seed)
+    y = np.random.default_rng(seed).uniform(-0.5, 0.5)
+    m = _rot_zyx(roll, pitch, yaw)
+    # the drive's attitudes are a few degrees: the trace is positive, w is the large component
+    w = 0.5 * np.sqrt(1.0 + m[0, 0] + m[1, 1] + m[2, 2])
+    q = np.array([(m[2, 1] - m[1, 2]) / (4.0 * w), (m[0, 2] - m[2, 0]) / (4.0 * w), (m[1, 0] - m[0, 1]) / (4.0 * w), w])
+    out = np.zeros(13, np.float64)
+    out[0:4] = q
+    out[4:7] = (0.5 * (seed % 64), y, dz)
+    return out
+
+
 def make_symmetric_scan(seed: int, lidar: str = VLP16, quadrants: int = 4) -> np.ndarray:
     """A scan whose first quarter of azimuth columns is repeated, rotated by 90 degrees about the
     sensor, in the other quarters (quadrants = 4) or half repeated at 180 degrees (quadrants = 2).
