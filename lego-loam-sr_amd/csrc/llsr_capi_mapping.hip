@@ -1,0 +1,428 @@
+// llsr_capi_mapping.hip — C-ABI host side of the mapping chain (MapOptimization::run, MO:1854-1896):
+// the odometry batch, then per slot the pose glue on the host (llsr_mapping.h) around batched
+// device work — adjustOutlierCloud, one segmented VoxelGrid for every slot's
+// downsampleCurrentScan, the slots' local maps, and one scan-to-map batch over all slots.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "llsr_handle.h"
+
+namespace llsr {
+// adjustOutlierCloud (FA:2600-2610): the IP outlier cloud of slot b (d.outl, [B][HW]) with
+// x, y, z <- y, z, x, packed at off[b].
+__global__ void k_mapping_outliers(const float4* outl, int HW, const int64_t* off, float4* out) {
+  const int b = blockIdx.y;
+  const int64_t o0 = off[b], n = off[b + 1] - o0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 p = outl[(size_t)b * HW + i];
+    out[o0 + i] = make_float4(p.y, p.z, p.x, p.w);
+  }
+}
+}  // namespace llsr
+
+using namespace llsr;
+
+// Grow a device point buffer to hold `need` points, keeping its first `keep` points.
+static int32_t mp_grow(llsr_handle* h, GrowBuf& buf, size_t need, size_t keep, hipStream_t s) {
+  if (need <= buf.cap && buf.mem) return LLSR_OK;
+  size_t n = buf.cap ? buf.cap : (size_t)1 << 16;
+  while (n < need) n *= 2;
+  llsr_host::DevMem q;
+  if (llsr_host::alloc(q, n * sizeof(float4)) != hipSuccess) return fail(h, LLSR_ENOMEM, "mapping buffers");
+  if (buf.mem && keep) HIP_OK(h, hipMemcpyAsync(q, buf.mem, keep * sizeof(float4), hipMemcpyDeviceToDevice, s));
+  HIP_OK(h, sync_handle_streams(h));
+  HIP_OK(h, hipStreamSynchronize(s));
+  buf.mem = std::move(q);  // frees the old buffer
+  buf.cap = n;
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_mapping_reset(llsr_handle* h) {
+  if (!h) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  int32_t rc = llsr_odometry_reset(h);
+  if (rc != LLSR_OK) return rc;
+  for (auto& sl : mp.slot) {
+    llsr_map* m = sl.map;
+    if (llsr_map_reset(m) != LLSR_OK) return fail(h, LLSR_EINVAL, "llsr_map_reset");
+    sl = llsr_handle::MapSlot{};
+    sl.map = m;
+  }
+  const int B = (int)mp.slot.size();
+  HIP_OK(h, hipMemset(mp.sm.d_deg, 0, sizeof(int) * B));      // isDegenerate = false (MO:285)
+  HIP_OK(h, hipMemset(mp.sm.d_matP, 0, sizeof(float) * 36 * B));  // matP zeroed (MO:286)
+  return LLSR_OK;
+}
+
+// (the point buffers outl / ds / tot / cmap stay: a later init reuses them)
+void mapping_free(llsr_handle* h) {
+  auto& mp = h->mp;
+  for (auto& sl : mp.slot)
+    if (sl.map) llsr_map_destroy(sl.map);
+  mp.slot.clear();
+  if (mp.vg) llsr_map_destroy(mp.vg);
+  mp.vg = nullptr;
+  mp.sm = llsr_handle::MapSmall{};
+  mp.live = false;
+}
+
+extern "C" int32_t llsr_mapping_init(llsr_handle* h, int32_t mo_mode, const llsr_map_config* map_cfg) {
+  if (!h) return LLSR_EINVAL;
+  if (mo_mode != LLSR_MODE_FAITHFUL && mo_mode != LLSR_MODE_LM_APPLIED) return fail(h, LLSR_EINVAL, "mo_mode");
+  // both handle modes: llsr_mapping_batch refuses the faithful one itself, llsr_mapping_batch_odom runs it
+  llsr_map_config mcfg;
+  if (map_cfg) mcfg = *map_cfg;  // NULL: the YAML block of the handle's lidar
+  else llsr_map_config_lidar(&mcfg, h->dc.H == 64 ? LLSR_LIDAR_HDL64E : LLSR_LIDAR_VLP16);
+  if (mcfg.enable_loop_closure && mcfg.surrounding_keyframe_search_num < 1)
+    return fail(h, LLSR_EINVAL, "surrounding_keyframe_search_num must be >= 1 with loop closure");
+  HIP_OK(h, hipSetDevice(h->device));
+  int32_t rc = odo_alloc(h);
+  if (rc != LLSR_OK) return rc;
+  auto& mp = h->mp;
+  HIP_OK(h, sync_handle_streams(h));
+  mapping_free(h);  // a repeated init rebuilds everything with the new map config
+  mp.mode = mo_mode;
+  mp.mcfg = mcfg;
+  const int B = h->max_batch;
+  mp.slot.resize(B);
+  for (auto& sl : mp.slot)
+    if (!(sl.map = llsr_map_create(&mp.mcfg, h->device))) { mapping_free(h); return fail(h, LLSR_ENOMEM, "llsr_map_create"); }
+  if (!(mp.vg = llsr_map_create(&mp.mcfg, h->device))) { mapping_free(h); return fail(h, LLSR_ENOMEM, "llsr_map_create"); }
+  llsr_handle::MapSmall sm;  // built aside: mp.sm stays empty unless both allocations succeed
+  if (llsr_host::alloc_pool(sm.dev, 0, [&](llsr_host::Carver& c) { llsr_host::mapping_layout(c, sm, B); }) != hipSuccess) {
+    mapping_free(h);
+    return fail(h, LLSR_ENOMEM, "mapping state");
+  }
+  if (llsr_host::alloc_pool(sm.host, 0, [&](llsr_host::Carver& c) { llsr_host::mapping_host_layout(c, sm, B); }) !=
+      hipSuccess) {
+    mapping_free(h);
+    return fail(h, LLSR_ENOMEM, "mapping staging");
+  }
+  mp.sm = std::move(sm);
+  mp.live = true;
+  return llsr_mapping_reset(h);
+}
+
+// MapOptimization::run for the slots in `step` (their pose glue already applied by the caller).
+static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::vector<char>& step) {
+  auto& mp = h->mp;
+  auto& o = h->odo;
+  int32_t rc = LLSR_OK;
+  const int NB = o.B, nb = NB + 1;
+  // this frame's AssociationOut clouds (the batch flipped o.cur to them)
+  const int64_t* hs = o.h_off;                     // cloud_corner_scan (sharp, TransformToEnd)
+  const int64_t* hf = o.h_off + nb;                // cloud_surf_scan (flat + shadow, TransformToEnd)
+  const int64_t* hlc = o.h_off + (2 + o.cur) * nb; // cloud_corner_last
+  const int64_t* hls = o.h_off + (4 + o.cur) * nb; // cloud_surf_last (+ shadow)
+  // adjustOutlierCloud of this frame's IP outliers (FA:2720)
+  int64_t* hol = mp.sm.h_off + 4 * (size_t)nb;
+  hol[0] = 0;
+  int maxO = 0;
+  for (int b = 0; b < NB; ++b) {
+    const int n = (b < B && step[b]) ? o.h_counts[(size_t)b * kCnt + C_O] : 0;
+    hol[b + 1] = hol[b] + n;
+    maxO = n > maxO ? n : maxO;
+  }
+  rc = mp_grow(h, mp.outl, (size_t)hol[NB] + 1, 0, s);
+  if (rc != LLSR_OK) return rc;
+  HIP_OK(h, hipMemcpyAsync(mp.sm.d_off + 4 * (size_t)nb, hol, sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
+  if (maxO > 0) {
+    const int gx = (maxO + 255) / 256 < 64 ? (maxO + 255) / 256 : 64;
+    k_mapping_outliers<<<dim3(gx, B), 256, 0, s>>>(h->d.outl, h->dc.HW, mp.sm.d_off + 4 * (size_t)nb, mp.outl.p());
+    HIP_OK(h, hipGetLastError());
+  }
+  // downsampleCurrentScan (MO:1234-1258) of every slot in one segmented VoxelGrid; segments by
+  // kind so each kind's per-slot results are contiguous: [corner last][surf last, outlier]...
+  // [corner scan][surf scan]
+  const float lc = mp.mcfg.corner_leaf, lsf = mp.mcfg.surf_leaf, lo = mp.mcfg.outlier_leaf;
+  const int S5 = 5 * NB;
+  std::vector<const float4*> src(S5);
+  std::vector<long long> cnt(S5, 0), dso(S5 + 1), toto(NB + 1);
+  std::vector<float> leaf(S5);
+  long long total = 0;
+  for (int b = 0; b < NB; ++b) {
+    const bool on = b < B && step[b];
+    src[b] = o.last_c[o.cur] + hlc[b];          cnt[b] = on ? hlc[b + 1] - hlc[b] : 0;          leaf[b] = lc;
+    src[NB + 2 * b] = o.last_s[o.cur] + hls[b]; cnt[NB + 2 * b] = on ? hls[b + 1] - hls[b] : 0; leaf[NB + 2 * b] = lsf;
+    src[NB + 2 * b + 1] = mp.outl.p() + hol[b];     cnt[NB + 2 * b + 1] = hol[b + 1] - hol[b];      leaf[NB + 2 * b + 1] = lo;
+    src[3 * NB + b] = o.scan_c + hs[b];         cnt[3 * NB + b] = on ? hs[b + 1] - hs[b] : 0;   leaf[3 * NB + b] = lc;
+    src[4 * NB + b] = o.scan_s + hf[b];         cnt[4 * NB + b] = on ? hf[b + 1] - hf[b] : 0;   leaf[4 * NB + b] = lsf;
+  }
+  for (long long c : cnt) total += c;
+  rc = mp_grow(h, mp.ds, (size_t)total + 1, 0, s);
+  if (rc != LLSR_OK) return rc;
+  rc = llsr_mapping::voxel_multi(mp.vg, src.data(), cnt.data(), leaf.data(), S5, mp.ds.p(), dso.data(), s);
+  if (rc != LLSR_OK) return fail(h, rc, std::string("downsample: ") + llsr_map_last_error(mp.vg));
+  // laserCloudSurfTotalLastDS = surf leaf over SurfLastDS + OutlierLastDS (MO:1260-1266)
+  std::vector<const float4*> tsrc(NB);
+  std::vector<long long> tcnt(NB);
+  std::vector<float> tleaf(NB, lsf);
+  for (int b = 0; b < NB; ++b) {
+    tsrc[b] = mp.ds.p() + dso[NB + 2 * b];
+    tcnt[b] = dso[NB + 2 * b + 2] - dso[NB + 2 * b];
+  }
+  rc = mp_grow(h, mp.tot, (size_t)(dso[3 * NB] - dso[NB]) + 1, 0, s);
+  if (rc != LLSR_OK) return rc;
+  rc = llsr_mapping::voxel_multi(mp.vg, tsrc.data(), tcnt.data(), tleaf.data(), NB, mp.tot.p(), toto.data(), s);
+  if (rc != LLSR_OK) return fail(h, rc, std::string("downsample: ") + llsr_map_last_error(mp.vg));
+  // extractSurroundingKeyFrames (MO:1096-1232) around currentRobotPosPoint, every slot with
+  // keyframes in one pass (a slot without keyframes keeps an empty local map, MO:1097)
+  std::vector<llsr_map*> emaps;
+  std::vector<int> eslot;
+  std::vector<float> epos;
+  for (int b = 0; b < B; ++b) {
+    auto& sl = mp.slot[b];
+    if (!step[b]) continue;
+    sl.mrep = llsr_map_report{};
+    sl.n_cq = (int)(dso[3 * NB + b + 1] - dso[3 * NB + b]);
+    sl.n_sq = (int)(toto[b + 1] - toto[b]);
+    if (llsr_map_num_keyframes(sl.map) == 0) continue;
+    emaps.push_back(sl.map);
+    eslot.push_back(b);
+    epos.insert(epos.end(), sl.robot, sl.robot + 3);
+  }
+  const int nE = (int)emaps.size();
+  std::vector<llsr_map_report> ereps(nE > 0 ? nE : 1);
+  std::vector<long long> eoc(nE + 1, 0), eos(nE + 1, 0);
+  const float4* lmap = nullptr;
+  if (nE > 0) {
+    rc = llsr_mapping::extract_multi(mp.vg, emaps.data(), nE, epos.data(), ereps.data(), &lmap, eoc.data(),
+                                     eos.data(), s);
+    if (rc != LLSR_OK) return fail(h, rc, std::string("extract: ") + llsr_map_last_error(mp.vg));
+  } else {
+    rc = mp_grow(h, mp.cmap, 1, 0, s);  // a valid (empty) map base for the batch
+    if (rc != LLSR_OK) return rc;
+    lmap = mp.cmap.p();
+  }
+  int64_t* hcq = mp.sm.h_off;
+  int64_t* hsq = mp.sm.h_off + nb;
+  int64_t* hmc = mp.sm.h_off + 2 * (size_t)nb;
+  int64_t* hms = mp.sm.h_off + 3 * (size_t)nb;
+  long long mMc = 1, mMs = 1, mQc = 1, mQs = 1;
+  {
+    long long cc = eoc[0], cs = eos[0];
+    int e = 0;
+    for (int b = 0; b < NB; ++b) {
+      hcq[b] = dso[3 * NB + b];
+      hsq[b] = toto[b];
+      hmc[b] = cc;
+      hms[b] = cs;
+      if (e < nE && eslot[e] == b) {
+        mp.slot[b].mrep = ereps[e];
+        cc = eoc[e + 1];
+        cs = eos[e + 1];
+        ++e;
+      }
+      mMc = std::max(mMc, (long long)(cc - hmc[b]));
+      mMs = std::max(mMs, (long long)(cs - hms[b]));
+      mQc = std::max(mQc, (long long)(dso[3 * NB + b + 1] - dso[3 * NB + b]));
+      mQs = std::max(mQs, (long long)(toto[b + 1] - toto[b]));
+    }
+    hmc[NB] = cc;
+    hms[NB] = cs;
+    hcq[NB] = dso[4 * NB];
+    hsq[NB] = toto[NB];
+  }
+  // scan2MapOptimization (MO:1572-1610): every slot is a problem; slots without a step, or whose
+  // map fails MO:1573, stay inactive and keep their pose and LM members
+  rc = llsr_scan2map_reserve(h, NB, (int32_t)mMc, (int32_t)mMs, (int32_t)mQc, (int32_t)mQs);
+  if (rc != LLSR_OK) return rc;
+  for (int b = 0; b < NB; ++b)
+    for (int k = 0; k < 6; ++k) mp.sm.h_pose[6 * b + k] = mp.slot[b].pose.transformTobeMapped[k];
+  HIP_OK(h, hipMemcpyAsync(mp.sm.d_pose, mp.sm.h_pose, sizeof(float) * 6 * NB, hipMemcpyHostToDevice, s));
+  HIP_OK(h, hipMemcpyAsync(mp.sm.d_off, mp.sm.h_off, sizeof(int64_t) * 4 * nb, hipMemcpyHostToDevice, s));
+  llsr_s2m_batch sb{};
+  sb.n_problems = NB;
+  sb.corner_q = (const float*)mp.ds.p(); sb.corner_q_off = mp.sm.d_off;
+  sb.surf_q = (const float*)mp.tot.p(); sb.surf_q_off = mp.sm.d_off + nb;
+  sb.corner_map = (const float*)lmap; sb.corner_map_off = mp.sm.d_off + 2 * (size_t)nb;
+  sb.surf_map = (const float*)lmap; sb.surf_map_off = mp.sm.d_off + 3 * (size_t)nb;
+  sb.pose = mp.sm.d_pose;
+  sb.report = mp.sm.d_rep;
+  S2MOpts opt;
+  opt.mode = mp.mode;
+  opt.deg_in = opt.deg_out = mp.sm.d_deg;
+  opt.matP_in = opt.matP_out = mp.sm.d_matP;
+  rc = s2m_batch(h, &sb, s, opt);
+  if (rc != LLSR_OK) return rc;
+  HIP_OK(h, hipMemcpyAsync(mp.sm.h_pose, mp.sm.d_pose, sizeof(float) * 6 * NB, hipMemcpyDeviceToHost, s));
+  HIP_OK(h, hipMemcpyAsync(mp.sm.h_rep, mp.sm.d_rep, sizeof(llsr_lm_report) * NB, hipMemcpyDeviceToHost, s));
+  HIP_OK(h, hipStreamSynchronize(s));
+  // transformUpdate (MO:1608) and saveKeyFramesAndFactor (MO:1612-1755)
+  for (int b = 0; b < B; ++b) {
+    if (!step[b]) continue;
+    auto& sl = mp.slot[b];
+    auto& P = sl.pose;
+    sl.lm = mp.sm.h_rep[b];
+    sl.lm_ran = (hmc[b + 1] - hmc[b] > 10 && hms[b + 1] - hms[b] > 100) ? 1 : 0;
+    if (sl.lm_ran) {
+      for (int k = 0; k < 6; ++k) P.transformTobeMapped[k] = mp.sm.h_pose[6 * b + k];
+      llsr_mapping::transform_update(P);
+    }
+    for (int k = 0; k < 3; ++k) sl.robot[k] = P.transformAftMapped[3 + k];
+    const bool first = llsr_map_num_keyframes(sl.map) == 0;
+    const float* est = first ? P.transformTobeMapped : P.transformAftMapped;  // iSAM2's latestEstimate
+    const float kp[6] = {est[3], est[4], est[5], est[0], est[1], est[2]};
+    for (int k = 0; k < 6; ++k) {
+      P.transformLast[k] = est[k];
+      if (!first) P.transformTobeMapped[k] = P.transformAftMapped[k];
+    }
+    const int kf = llsr_map_add_keyframe(
+        sl.map, kp, (const float*)(o.scan_c + hs[b]), (int32_t)(hs[b + 1] - hs[b]),
+        (const float*)(mp.ds.p() + dso[NB + 2 * b]), (int32_t)(dso[NB + 2 * b + 1] - dso[NB + 2 * b]),
+        (const float*)(mp.ds.p() + dso[NB + 2 * b + 1]), (int32_t)(dso[NB + 2 * b + 2] - dso[NB + 2 * b + 1]), s);
+    if (kf < 0) return fail(h, kf, std::string("add_keyframe: ") + llsr_map_last_error(sl.map));
+    sl.keyposes.insert(sl.keyposes.end(), kp, kp + 6);
+    sl.mo_frames += 1;
+  }
+#ifdef LLSR_S2S_PROF
+  {  // diagnostics build only: fail this call's MapOptimization part once, after its keyframes were
+     // added, when slot 0 reaches MapOptimization frame LLSR_MO_FAIL_AT (tests/test_gpu_mapping_rollback.py)
+    static bool fired = false;
+    const char* at = std::getenv("LLSR_MO_FAIL_AT");
+    if (at && !fired && step[0] && mp.slot[0].mo_frames == std::atoi(at)) {
+      fired = true;
+      return fail(h, LLSR_EIO, "injected MapOptimization failure (LLSR_MO_FAIL_AT)");
+    }
+  }
+#endif
+  return LLSR_OK;
+}
+
+// llsr_mapping_batch (samples == nullptr) and llsr_mapping_batch_odom
+static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                             const llsr_odom_sample* samples, const uint8_t* overwrite, void* hip_stream) {
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (B < 1 || B > h->max_batch) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
+  hipStream_t s;
+  HIP_OK(h, enter(h, hip_stream, &s));
+  int32_t rc = odo_batch(h, d_xyzi, d_offsets, B, samples, overwrite, s);
+  if (rc != LLSR_OK) return rc;
+  auto& o = h->odo;
+  HIP_OK(h, hipMemcpyAsync(mp.sm.h_frames, o.frames, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+  HIP_OK(h, hipMemcpyAsync(mp.sm.h_tsum, o.tsum, sizeof(float) * 6 * B, hipMemcpyDeviceToHost, s));
+  HIP_OK(h, hipStreamSynchronize(s));
+  rc = llsr_scan2scan_check(h);
+  if (rc != LLSR_OK) return rc;
+  // MapOptimization's members of the B slots before this frame: an error below restores them
+  struct Snap {
+    llsr_handle::MapSlot slot;  // (keyposes: only its length is restored)
+    size_t n_keyposes;
+    int n_keyframes;
+    llsr_mapping::MapSel sel;
+  };
+  std::vector<Snap> snap(B);
+  for (int b = 0; b < B; ++b) {
+    const auto& sl = mp.slot[b];
+    snap[b].slot.pose = sl.pose;
+    std::memcpy(snap[b].slot.robot, sl.robot, sizeof sl.robot);
+    snap[b].slot.mo_frames = sl.mo_frames; snap[b].slot.lm_ran = sl.lm_ran;
+    snap[b].slot.n_cq = sl.n_cq; snap[b].slot.n_sq = sl.n_sq; snap[b].slot.cycle = sl.cycle;
+    snap[b].slot.lm = sl.lm; snap[b].slot.mrep = sl.mrep;
+    snap[b].n_keyposes = sl.keyposes.size();
+    snap[b].n_keyframes = llsr_map_num_keyframes(sl.map);
+    snap[b].sel = llsr_mapping::map_selection(sl.map);
+  }
+  std::vector<char> step(o.B, 0);  // slots that receive an AssociationOut this call
+  for (int b = 0; b < B; ++b) {
+    auto& sl = mp.slot[b];
+    sl.frames = mp.sm.h_frames[b];
+    // FA:2781-2784: the first scan sends nothing; FA:2818-2821: every mapping_frequency_divider-th
+    // frame after it sends an AssociationOut
+    if (sl.frames >= 2 && ++sl.cycle == h->cfg.mapping_frequency_divider) {
+      sl.cycle = 0;
+      step[b] = 1;
+    }
+    if (!step[b]) continue;
+    llsr_mapping::odometry_roundtrip(mp.sm.h_tsum + 6 * b, sl.pose.transformSum);  // OdometryToTransform
+    llsr_mapping::transform_associate_to_map(sl.pose);
+  }
+  bool any = false;
+  for (char c : step) any |= c != 0;
+  if (any) {  // the LM members (isDegenerate, matP) before this frame, restored if it fails
+    HIP_OK(h, hipMemcpyAsync(mp.sm.d_deg_bak, mp.sm.d_deg, sizeof(int) * o.B, hipMemcpyDeviceToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(mp.sm.d_matP_bak, mp.sm.d_matP, sizeof(float) * 36 * o.B, hipMemcpyDeviceToDevice, s));
+  }
+  rc = any ? mapping_mo(h, B, s, step) : LLSR_OK;
+  if (rc != LLSR_OK) {
+    const std::string msg = h->err;
+    (void)hipStreamSynchronize(s);
+    for (int b = 0; b < B; ++b) {
+      auto& sl = mp.slot[b];
+      const auto& sn = snap[b].slot;
+      sl.pose = sn.pose;
+      std::memcpy(sl.robot, sn.robot, sizeof sl.robot);
+      sl.mo_frames = sn.mo_frames; sl.lm_ran = sn.lm_ran; sl.n_cq = sn.n_cq; sl.n_sq = sn.n_sq;
+      sl.cycle = sn.cycle; sl.lm = sn.lm; sl.mrep = sn.mrep;
+      sl.keyposes.resize(snap[b].n_keyposes);
+      llsr_mapping::truncate_keyframes(sl.map, snap[b].n_keyframes);
+      llsr_mapping::set_map_selection(sl.map, snap[b].sel);
+    }
+    (void)hipMemcpy(mp.sm.d_deg, mp.sm.d_deg_bak, sizeof(int) * o.B, hipMemcpyDeviceToDevice);
+    (void)hipMemcpy(mp.sm.d_matP, mp.sm.d_matP_bak, sizeof(float) * 36 * o.B, hipMemcpyDeviceToDevice);
+    return fail(h, rc, msg);
+  }
+  HIP_OK(h, hipEventRecord(h->last_done, s));
+  h->last_rec = true;
+  h->last_stream = s;
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                                      void* hip_stream) {
+  if (!h) return LLSR_EINVAL;
+  if (h->cfg.mode != LLSR_MODE_LM_APPLIED)
+    return fail(h, LLSR_ENOSYS, "the mapping chain runs the odometry, which needs LLSR_MODE_LM_APPLIED "
+                                "(llsr_mapping_batch_odom takes the /odom2 input of the faithful mode)");
+  return mapping_batch(h, d_xyzi, d_offsets, B, nullptr, nullptr, hip_stream);
+}
+
+extern "C" int32_t llsr_mapping_batch_odom(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
+                                           const llsr_odom_sample* samples, const uint8_t* overwrite,
+                                           void* hip_stream) {
+  if (!h) return LLSR_EINVAL;
+  if (!samples) return fail(h, LLSR_EINVAL, "llsr_mapping_batch_odom: samples is NULL");
+  return mapping_batch(h, d_xyzi, d_offsets, B, samples, overwrite, hip_stream);
+}
+
+extern "C" int32_t llsr_mapping_fetch(llsr_handle* h, int32_t b, llsr_mapping_slot* out) {
+  if (!h || !out) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (b < 0 || b >= (int)mp.slot.size()) return fail(h, LLSR_ERANGE, "slot outside [0, max_batch)");
+  const auto& sl = mp.slot[b];
+  std::memset(out, 0, sizeof *out);
+  out->frames = sl.frames;
+  out->mo_frames = sl.mo_frames;
+  out->keyframes = (int32_t)(sl.keyposes.size() / 6);
+  out->lm_ran = sl.lm_ran;
+  for (int k = 0; k < 6; ++k) {
+    out->transform_sum[k] = sl.pose.transformSum[k];
+    out->transform_tobe_mapped[k] = sl.pose.transformTobeMapped[k];
+    out->transform_bef_mapped[k] = sl.pose.transformBefMapped[k];
+    out->transform_aft_mapped[k] = sl.pose.transformAftMapped[k];
+  }
+  out->n_corner_q = sl.n_cq;
+  out->n_surf_q = sl.n_sq;
+  out->lm = sl.lm;
+  out->map = sl.mrep;
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_mapping_keyposes(llsr_handle* h, int32_t b, float* out, int32_t cap) {
+  if (!h) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (b < 0 || b >= (int)mp.slot.size()) return fail(h, LLSR_ERANGE, "slot outside [0, max_batch)");
+  const auto& kp = mp.slot[b].keyposes;
+  const int n = (int)(kp.size() / 6);
+  if (out && cap > 0) std::memcpy(out, kp.data(), sizeof(float) * 6 * (size_t)(n < cap ? n : cap));
+  return n;
+}

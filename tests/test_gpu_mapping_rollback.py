@@ -1,6 +1,6 @@
 """GPU: llsr_mapping_batch's error contract (include/llsr.h: an error from the MapOptimization part of
 a call, after the odometry advanced, leaves every slot's MapOptimization members as before the
-call — the snapshot / restore in llsr_capi.hip's llsr_mapping_batch).
+call — the snapshot / restore in llsr_capi_mapping.hip's mapping_batch).
 
 No input makes MapOptimization fail on purpose, so the diagnostics build (libllsr_prof.so, built
 with LLSR_S2S_PROF by `make`) fails it once on request: LLSR_MO_FAIL_AT=k fails the call in which
