@@ -466,6 +466,74 @@ int32_t llsr_map_extract(llsr_map* m, const float robot_pos[3], float* d_corner,
  * last extract; returns its length. */
 int32_t llsr_map_keyframe_ids(const llsr_map* m, int32_t* out, int32_t cap);
 
+/* ---- The global map: publishGlobalMap (MO:775-892) and saveMapService (MO:344-434) ----
+ * MapOptimization's third thread (publishGlobalMapThread, MO:305-315) and its end-of-run product, on
+ * the map's keyframe store. publishGlobalMap, in program order:
+ *  1. nothing happens without key poses (MO:780);
+ *  2. kdtreeGlobalMap.radiusSearch around the robot with sorted results (nanoflann_pcl.h:113-116,
+ *     165-167): key poses with d^2 = ((0 + dx^2) + dy^2) + dz^2 < float(double(r) * double(r)), in
+ *     ascending d^2. Tie divergence (as for the kNN): among exactly equal d^2 the
+ *     reference's order follows its kd-tree traversal and std::sort; here it is ascending key index;
+ *  3. unless high_dense, VoxelGrid keypose_leaf of those poses (x, y, z, intensity = key index) —
+ *     but `globalMapKeyPosesDS = globalMapKeyPoses` (MO:807) re-points the shared pointer, so the
+ *     first call's filter output lands in an orphaned cloud and the raw sorted list is used; from
+ *     the second call on both names are one cloud, pcl::Filter::filter works in place, and the
+ *     downsampled poses are used;
+ *  4. for every pose of that list, keyframe (int)intensity (after the filter: the voxel's mean key
+ *     index, truncated; two voxels may name one keyframe, which is then appended twice):
+ *     edge += corner, planar += surf, global += corner, surf, outlier (transformPointCloud);
+ *  5. unless high_dense, VoxelGrid cloud_leaf of the global cloud, with the same pointer behaviour
+ *     (MO:836): raw on the first call, downsampled later; PCL returns its input unchanged when the
+ *     voxel-extent product exceeds INT32_MAX (`passthrough`), which a 5000 m radius at a 0.4 m
+ *     leaf makes realistic;
+ *  6. the published clouds are global, edge and planar; the latter two are never downsampled.
+ * The call-to-call state is one counter per llsr_map: calls that returned LLSR_OK on a non-empty
+ * store since llsr_map_create / llsr_map_reset (an empty store returns before the pointers move,
+ * MO:780, and counts nothing). */
+typedef struct llsr_global_map_config {
+  float search_radius;    /* global_map_visualization_search_radius, 5000 (CFG:37) */
+  float keypose_leaf;     /* downSizeFilterGlobalMapKeyPoses, 1.0 (MO:102) */
+  float cloud_leaf;       /* downSizeFilterGlobalMapKeyFrames, 0.4 (MO:104) */
+  int32_t high_dense;     /* HighDenseMapping (CFG:40): no VoxelGrid at all */
+  int32_t first_call_raw; /* 1 = the reference's pointer behaviour (steps 3, 5);
+                             0 = downsample on every call */
+} llsr_global_map_config;
+typedef struct llsr_global_map_report {
+  int32_t call;           /* 1-based count of successful calls since create / reset (a refused or
+                             empty-store call reports the count so far) */
+  int32_t n_in_radius, n_poses_used;   /* used = list length of step 4, duplicates counted */
+  int32_t downsampled_poses, downsampled_cloud, passthrough;  /* what steps 3 / 5 did; PCL overflow */
+  int64_t n_edge, n_planar, n_global_raw, n_global;
+  float ms;               /* wall time of the call */
+} llsr_global_map_report;
+/* The largest cloud the VoxelGrid engine takes (its point indices are 32-bit); a larger global or
+ * surface cloud to downsample returns LLSR_ERANGE. */
+#define LLSR_VOXEL_GRID_MAX_POINTS 2147483646
+int32_t llsr_global_map_config_default(llsr_global_map_config* cfg);
+/* Steps 1-6 around robot_pos (currentRobotPosPoint, MO:1613-1615); cfg NULL = the defaults. Outputs
+ * are device float4 clouds, capacities in points; a NULL output with capacity 0 skips that cloud,
+ * its count is still reported (for a downsampled global cloud the VoxelGrid then runs in the map's
+ * scratch). When a requested capacity is too small the call returns LLSR_ERANGE with the sizes in
+ * rep (n_global is the upper bound n_global_raw when the refusal came before the VoxelGrid ran),
+ * leaves the outputs unspecified and does not advance the call counter, so a retry with larger
+ * buffers gives the identical result. cap_global >= n_global_raw lets the VoxelGrid write straight
+ * into d_global. Synchronises hip_stream. Uses the map's VoxelGrid scratch and assembly buffers:
+ * must not overlap llsr_map_add_keyframe, llsr_map_extract or any other call on the same map. */
+int32_t llsr_map_global(llsr_map* m, const llsr_global_map_config* cfg, const float robot_pos[3], float* d_global,
+                        int64_t cap_global, float* d_edge, int64_t cap_edge, float* d_planar, int64_t cap_planar,
+                        llsr_global_map_report* rep, void* hip_stream);
+/* saveMapService's clouds in the save_key_feature_pcd == false branch every config block uses
+ * (MO:382-395), over all keyframes in index order: cornerMap = the transformed corner clouds (raw,
+ * as written); surfaceMap = per keyframe the transformed surf cloud then the outlier cloud, through
+ * downSizeFilterSurf (the map's surf_leaf). Same output, capacity, LLSR_ERANGE (*n_surf then an
+ * upper bound or the exact size) and overlap rules as llsr_map_global; no call-to-call state. */
+int32_t llsr_map_save(llsr_map* m, float* d_corner, int64_t cap_corner, float* d_surf, int64_t cap_surf,
+                      int64_t* n_corner, int64_t* n_surf, void* hip_stream);
+/* Host-only (no device): the selection of step 2 over K poses (x, y, z, anything) into out_idx[K];
+ * returns the count. */
+int32_t llsr_keypose_radius_sorted(const float* poses4, int32_t K, const float pos[3], float radius,
+                                   int32_t* out_idx);
+
 /* ---- Mapping chain: ImageProjection -> FeatureAssociation -> MapOptimization::run ----
  * (mapOptmization.cpp:1854-1896.) Each llsr_mapping_batch call runs llsr_odometry_batch on the B
  * slots and then, for every slot that sends an AssociationOut this frame — FA counts the frames
@@ -510,8 +578,15 @@ int32_t llsr_mapping_fetch(llsr_handle* h, int32_t b, llsr_mapping_slot* out);
 /* cloudKeyPoses6D of slot b: x, y, z, roll, pitch, yaw per keyframe into out[6*cap]; returns the
  * keyframe count (may exceed cap). */
 int32_t llsr_mapping_keyposes(llsr_handle* h, int32_t b, float* out, int32_t cap);
-/* Start every slot over: odometry, poses, keyframe stores. */
+/* Start every slot over: odometry, poses, keyframe stores, the global map's call counters. */
 int32_t llsr_mapping_reset(llsr_handle* h);
+/* llsr_map_global / llsr_map_save on slot b's keyframe store, after the handle's pending work;
+ * robot_pos is the slot's transform_aft_mapped[3..5]. One call counter per slot. */
+int32_t llsr_mapping_global_map(llsr_handle* h, int32_t b, const llsr_global_map_config* cfg, float* d_global,
+                                int64_t cap_global, float* d_edge, int64_t cap_edge, float* d_planar,
+                                int64_t cap_planar, llsr_global_map_report* rep, void* hip_stream);
+int32_t llsr_mapping_save_map(llsr_handle* h, int32_t b, float* d_corner, int64_t cap_corner, float* d_surf,
+                              int64_t cap_surf, int64_t* n_corner, int64_t* n_surf, void* hip_stream);
 /* Host-only (no device): the pose glue llsr_mapping_batch applies per frame — OdometryToTransform
  * of FA's transformSum (tf2 round trip) into transform_sum, then transformAssociateToMap with the
  * given transformBefMapped / transformAftMapped into transform_tobe_mapped (and transform_incre,

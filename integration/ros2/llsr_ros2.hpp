@@ -15,6 +15,7 @@
 //   FeatureAssociation::updateInitialGuess   featureAssociation.cpp:2337-2402 -> OdomInput::apply
 //   FeatureAssociation::updateTransformation featureAssociation.cpp:2505-2535 -> update_transformation
 //   MapOptimization::scan2MapOptimization    mapOptmization.cpp:1572-1610 -> scan2map_optimization
+//   MapOptimization::publishGlobalMapThread  mapOptmization.cpp:305-315, 775-892 -> GlobalMap (opt-in)
 //
 // Threads. The reference runs IP, FA and MO on their own executor threads joined by one-slot
 // Channels (main.cpp:10-11, channel.h:24-54); IP's blocking send waits only until FA has *taken*
@@ -34,6 +35,9 @@
 #include <vector>
 
 #include "llsr.h"
+#ifdef LLSR_ROS2_GLOBAL_MAP
+#include <hip/hip_runtime_api.h>
+#endif
 
 namespace llsr_ros2 {
 
@@ -447,5 +451,73 @@ llsr_lm_report scan2map_optimization(llsr_handle* h, const Cloud& corner_scan_ds
         h, "llsr_scan2map");
   return rep;
 }
+
+#ifdef LLSR_ROS2_GLOBAL_MAP
+// publishGlobalMapThread (MO:305-315) over llsr_map_global. Opt-in (define LLSR_ROS2_GLOBAL_MAP
+// before including this header and link the HIP runtime): the helper owns the three device output
+// buffers, which the rest of this header has no need for. run() counts its iterations and signals
+// the thread on every fifth (MO:1913-1921): on_cycle() once per run() iteration, publish() when it
+// returns true. The call counter that makes the first publish raw lives in the llsr_map.
+template <class Cloud>
+class GlobalMap {
+ public:
+  explicit GlobalMap(const llsr_global_map_config* cfg = nullptr) {
+    if (cfg) cfg_ = *cfg;
+    else check(llsr_global_map_config_default(&cfg_), nullptr, "llsr_global_map_config_default");
+  }
+  ~GlobalMap() {
+    for (int k = 0; k < 3; ++k)
+      if (dev_[k]) (void)hipFree(dev_[k]);
+  }
+  GlobalMap(const GlobalMap&) = delete;
+  GlobalMap& operator=(const GlobalMap&) = delete;
+
+  bool on_cycle() { return ++cycle_count_ % 5 == 0; }
+
+  // publishGlobalMap (MO:775-892) around robot_pos (currentRobotPosPoint): the clouds of
+  // /laser_cloud_surround, the edge feature map and the planar feature map. Must not overlap
+  // another call on `m` (the reference takes mtx around its own use of the key poses, MO:785-790).
+  void publish(llsr_map* m, const float robot_pos[3]) {
+    for (int k = 0; k < 3; ++k) reserve(k, 1);  // a NULL output would be skipped
+    int32_t rc = LLSR_ERANGE;
+    for (int attempt = 0; attempt < 2 && rc == LLSR_ERANGE; ++attempt) {
+      rc = llsr_map_global(m, &cfg_, robot_pos, dev_[0], cap_[0], dev_[1], cap_[1], dev_[2], cap_[2], &report, nullptr);
+      if (rc != LLSR_ERANGE) break;
+      const int64_t need[3] = {report.n_global, report.n_edge, report.n_planar};
+      for (int k = 0; k < 3; ++k) reserve(k, need[k]);
+    }
+    if (rc != LLSR_OK) throw std::runtime_error(std::string("llsr: llsr_map_global: ") + llsr_map_last_error(m));
+    fetch(0, report.n_global, global);
+    fetch(1, report.n_edge, edge);
+    fetch(2, report.n_planar, planar);
+  }
+
+  Cloud global, edge, planar;  // globalMapKeyFrames, edgeMapKeyFrames, planarMapKeyFrames
+  llsr_global_map_report report = llsr_global_map_report();
+
+ private:
+  void reserve(int k, int64_t need) {
+    if (need <= cap_[k]) return;
+    if (dev_[k] && hipFree(dev_[k]) != hipSuccess) throw std::runtime_error("llsr: hipFree");
+    dev_[k] = nullptr;
+    cap_[k] = 0;
+    void* p = nullptr;
+    if (hipMalloc(&p, (size_t)need * 4 * sizeof(float)) != hipSuccess) throw std::runtime_error("llsr: hipMalloc");
+    dev_[k] = static_cast<float*>(p);
+    cap_[k] = need;
+  }
+  void fetch(int k, int64_t n, Cloud& c) {
+    host_[k].resize(4 * (size_t)n);
+    if (n && hipMemcpy(host_[k].data(), dev_[k], (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("llsr: hipMemcpy");
+    unpack_xyzi(host_[k].data(), (int32_t)n, c);
+  }
+  llsr_global_map_config cfg_;
+  int cycle_count_ = 0;
+  float* dev_[3] = {nullptr, nullptr, nullptr};  // global, edge, planar
+  int64_t cap_[3] = {0, 0, 0};
+  std::vector<float> host_[3];
+};
+#endif  // LLSR_ROS2_GLOBAL_MAP
 
 }  // namespace llsr_ros2

@@ -416,6 +416,41 @@ extern "C" int32_t llsr_mapping_fetch(llsr_handle* h, int32_t b, llsr_mapping_sl
   return LLSR_OK;
 }
 
+// publishGlobalMap / saveMapService on slot b's store (llsr_map.hip), after the handle's own streams
+static int32_t mapping_slot_map(llsr_handle* h, int32_t b, llsr_handle::MapSlot** sl) {
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (b < 0 || b >= (int)mp.slot.size()) return fail(h, LLSR_ERANGE, "slot outside [0, max_batch)");
+  HIP_OK(h, hipSetDevice(h->device));
+  HIP_OK(h, sync_handle_streams(h));
+  *sl = &mp.slot[b];
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_mapping_global_map(llsr_handle* h, int32_t b, const llsr_global_map_config* cfg,
+                                           float* d_global, int64_t cap_global, float* d_edge, int64_t cap_edge,
+                                           float* d_planar, int64_t cap_planar, llsr_global_map_report* rep,
+                                           void* hip_stream) {
+  if (!h || !rep) return LLSR_EINVAL;
+  llsr_handle::MapSlot* sl = nullptr;
+  int32_t rc = mapping_slot_map(h, b, &sl);
+  if (rc != LLSR_OK) return rc;
+  rc = llsr_map_global(sl->map, cfg, sl->pose.transformAftMapped + 3, d_global, cap_global, d_edge, cap_edge,
+                       d_planar, cap_planar, rep, hip_stream);
+  return rc == LLSR_OK ? rc : fail(h, rc, std::string("global map: ") + llsr_map_last_error(sl->map));
+}
+
+extern "C" int32_t llsr_mapping_save_map(llsr_handle* h, int32_t b, float* d_corner, int64_t cap_corner,
+                                         float* d_surf, int64_t cap_surf, int64_t* n_corner, int64_t* n_surf,
+                                         void* hip_stream) {
+  if (!h) return LLSR_EINVAL;
+  llsr_handle::MapSlot* sl = nullptr;
+  int32_t rc = mapping_slot_map(h, b, &sl);
+  if (rc != LLSR_OK) return rc;
+  rc = llsr_map_save(sl->map, d_corner, cap_corner, d_surf, cap_surf, n_corner, n_surf, hip_stream);
+  return rc == LLSR_OK ? rc : fail(h, rc, std::string("save map: ") + llsr_map_last_error(sl->map));
+}
+
 extern "C" int32_t llsr_mapping_keyposes(llsr_handle* h, int32_t b, float* out, int32_t cap) {
   if (!h) return LLSR_EINVAL;
   auto& mp = h->mp;

@@ -2,7 +2,9 @@
 // (saveKeyFramesAndFactor, mapOptmization.cpp:1686-1752), extractSurroundingKeyFrames in both of
 // its branches (the loop-closure queue of recent keyframes MO:1099-1151, the key-pose radius search
 // MO:1152-1223) with the local-map VoxelGrids (MO:1224-1231), downsampleCurrentScan
-// (MO:1234-1267), and the segmented VoxelGrid they all run on.
+// (MO:1234-1267), the global map (publishGlobalMap MO:775-892 and saveMapService's two clouds
+// MO:382-395: llsr_map_global / llsr_map_save at the end of this file, one assembly kernel
+// k_global_assemble), and the segmented VoxelGrid they all run on.
 //
 // VoxelGrid (pcl::VoxelGrid<PointXYZI>::applyFilter, PCL 1.10, downsample_all_data) of S clouds at
 // once, every step a device pass over HBM:
@@ -24,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <cfloat>
 #include <chrono>
 #include <cstdint>
@@ -338,7 +341,20 @@ __global__ void k_vg_offsets(const long long* base, const int* flag, const int* 
   out_off[s] = b < N ? (long long)rank[b] : total;
 }
 
-// transformPointCloud(cloudIn, transformIn) (MO:671-701) of one keyframe chunk per block.
+// transformPointCloud(cloudIn, transformIn) (MO:671-701): the one statement of its arithmetic, used
+// by the local map's k_map_transform and the global map's k_global_assemble alike.
+struct XfTrig { float cy, sy, cr, sr, cp, sp; };
+__device__ __forceinline__ float4 xf_point(const XfTrig& g, float tx, float ty, float tz, const float4 q) {
+  const float x1 = g.cy * q.x - g.sy * q.y;
+  const float y1 = g.sy * q.x + g.cy * q.y;
+  const float z1 = q.z;
+  const float x2 = x1;
+  const float y2 = g.cr * y1 - g.sr * z1;
+  const float z2 = g.sr * y1 + g.cr * z1;
+  return make_float4(g.cp * x2 + g.sp * z2 + tx, y2 + ty, -g.sp * x2 + g.cp * z2 + tz, q.w);
+}
+
+// One keyframe chunk per block.
 struct XfChunk {
   const float4* src;   // keyframe cloud chunk in its map's store
   long long dst;       // offset in the assembled map (points)
@@ -349,17 +365,43 @@ struct XfChunk {
 __global__ __launch_bounds__(256) void k_map_transform(const XfChunk* ch, float4* map) {
   const XfChunk c = ch[blockIdx.x];
   const float tx = c.t[0], ty = c.t[1], tz = c.t[2], roll = c.t[3], pitch = c.t[4], yaw = c.t[5];
-  const float cy = cosf_(yaw), sy = sinf_(yaw), cr = cosf_(roll), sr = sinf_(roll), cp = cosf_(pitch),
-              sp = sinf_(pitch);
-  for (int k = threadIdx.x; k < c.n; k += blockDim.x) {
-    const float4 q = c.src[k];
-    const float x1 = cy * q.x - sy * q.y;
-    const float y1 = sy * q.x + cy * q.y;
-    const float z1 = q.z;
-    const float x2 = x1;
-    const float y2 = cr * y1 - sr * z1;
-    const float z2 = sr * y1 + cr * z1;
-    map[c.dst + k] = make_float4(cp * x2 + sp * z2 + tx, y2 + ty, -sp * x2 + cp * z2 + tz, q.w);
+  const XfTrig g{cosf_(yaw), sinf_(yaw), cosf_(roll), sinf_(roll), cosf_(pitch), sinf_(pitch)};
+  for (int k = threadIdx.x; k < c.n; k += blockDim.x) map[c.dst + k] = xf_point(g, tx, ty, tz, c.src[k]);
+}
+
+// The global map's assembly (publishGlobalMap MO:809-823, saveMapService MO:382-395): every listed
+// keyframe's corner / surf / outlier cloud is read once and written, transformed by its key pose,
+// to up to two places: its feature cloud (dst1: edge for corner, planar for surf; the save layout
+// also sends outlier to planar) and the global cloud (dst2). A negative offset skips a destination.
+struct GmKf {
+  float t[6];             // x, y, z, roll, pitch, yaw
+  int n[3], pad;          // corner, surf, outlier points
+  long long src[3];       // offsets in the store
+  long long dst1[3];      // offsets in the edge (source 0) / planar (sources 1, 2) cloud
+  long long dst2[3];      // offsets in the global cloud
+};
+struct GmChunk { int kf, a, b, n; };  // points [b, b + n) of source a of listed keyframe kf, n <= 1024
+constexpr int kGmChunk = 1024;
+
+__global__ __launch_bounds__(256) void k_global_assemble(const GmChunk* ch, const GmKf* kfs, const float4* store,
+                                                         float4* edge, float4* planar, float4* global) {
+  const GmChunk c = ch[blockIdx.x];
+  const GmKf& k = kfs[c.kf];
+  __shared__ float tr[6];  // cy, sy, cr, sr, cp, sp: once per block
+  if (threadIdx.x < 6) {
+    const float a = threadIdx.x < 2 ? k.t[5] : (threadIdx.x < 4 ? k.t[3] : k.t[4]);  // yaw, roll, pitch
+    tr[threadIdx.x] = (threadIdx.x & 1) ? sinf_(a) : cosf_(a);
+  }
+  __syncthreads();
+  const XfTrig g{tr[0], tr[1], tr[2], tr[3], tr[4], tr[5]};
+  const float tx = k.t[0], ty = k.t[1], tz = k.t[2];
+  const float4* src = store + k.src[c.a] + c.b;
+  float4* d1 = k.dst1[c.a] < 0 ? nullptr : (c.a == 0 ? edge : planar) + k.dst1[c.a] + c.b;
+  float4* d2 = k.dst2[c.a] < 0 ? nullptr : global + k.dst2[c.a] + c.b;
+  for (int i = threadIdx.x; i < c.n; i += 256) {
+    const float4 p = xf_point(g, tx, ty, tz, src[i]);
+    if (d1) d1[i] = p;
+    if (d2) d2[i] = p;
   }
 }
 
@@ -424,6 +466,9 @@ struct llsr_map {
   char* isbuf = nullptr;       // exact introsort: range lists + counters
   size_t cap_isbuf = 0;
   int* hcnt = nullptr;         // pinned counters
+  // publishGlobalMap's call-to-call state: successful llsr_map_global calls since create / reset
+  // (the reference's re-pointed globalMapKeyPosesDS / globalMapKeyFramesDS, MO:807, 836)
+  int gm_calls = 0;
 };
 
 static int32_t mfail(llsr_map* m, int32_t code, const std::string& msg) {
@@ -670,6 +715,7 @@ extern "C" int32_t llsr_map_reset(llsr_map* m) {
   m->kf.clear();
   m->sel = llsr_mapping::MapSel{};
   m->store_used = 0;
+  m->gm_calls = 0;
   return LLSR_OK;
 }
 
@@ -952,4 +998,222 @@ extern "C" int32_t llsr_map_keyframe_ids(const llsr_map* m, int32_t* out, int32_
   const int n = (int)m->sel.ids.size();
   for (int k = 0; k < n && k < cap; ++k) out[k] = m->sel.ids[k];
   return n;
+}
+
+// ---- the global map: publishGlobalMap (MO:775-892) and saveMapService (MO:344-434) -------------
+extern "C" int32_t llsr_global_map_config_default(llsr_global_map_config* c) {
+  if (!c) return LLSR_EINVAL;
+  c->search_radius = 5000.0f;  // CFG:37
+  c->keypose_leaf = 1.0f;      // MO:102
+  c->cloud_leaf = 0.4f;        // MO:104
+  c->high_dense = 0;           // CFG:40
+  c->first_call_raw = 1;
+  return LLSR_OK;
+}
+
+// kdtreeGlobalMap.radiusSearch with sorted results (MO:787-789; nanoflann_pcl.h:113-116, 165-167):
+// d^2 = ((0 + dx^2) + dy^2) + dz^2 < float(r^2), ascending d^2, equal d^2 in ascending key index.
+extern "C" int32_t llsr_keypose_radius_sorted(const float* poses4, int32_t K, const float pos[3], float radius,
+                                              int32_t* out_idx) {
+  if (K < 0 || !pos || (K > 0 && (!poses4 || !out_idx))) return LLSR_EINVAL;
+  const float r2 = (float)((double)radius * (double)radius);
+  std::vector<std::pair<float, int32_t>> v;
+  for (int32_t k = 0; k < K; ++k) {
+    float d = 0;
+    for (int a = 0; a < 3; ++a) {
+      const float df = pos[a] - poses4[4 * (size_t)k + a];
+      d += df * df;
+    }
+    if (d < r2) v.push_back({d, k});
+  }
+  std::stable_sort(v.begin(), v.end(),
+                   [](const std::pair<float, int32_t>& x, const std::pair<float, int32_t>& y) { return x.first < y.first; });
+  for (size_t i = 0; i < v.size(); ++i) out_idx[i] = v[i].second;
+  return (int32_t)v.size();
+}
+
+namespace {
+
+// The descriptor table of `list` (keyframe indices, repeats allowed) with destinations laid out
+// keyframe by keyframe: source a goes to first[a] (0 edge, 1 planar, -1 none) and, with `global`,
+// to the global cloud as corner, surf, outlier. Returns the three cloud sizes in tot[3].
+std::vector<GmKf> gm_table(const llsr_map* m, const std::vector<int>& list, const int first[3], bool want_edge,
+                           bool want_planar, bool global, long long tot[3]) {
+  std::vector<GmKf> kfs(list.size());
+  tot[0] = tot[1] = tot[2] = 0;
+  for (size_t i = 0; i < list.size(); ++i) {
+    const llsr_map::Kf& k = m->kf[list[i]];
+    GmKf& g = kfs[i];
+    std::memcpy(g.t, k.pose, sizeof g.t);
+    g.pad = 0;
+    for (int a = 0; a < 3; ++a) {
+      g.n[a] = k.n[a];
+      g.src[a] = k.off[a];
+      g.dst1[a] = g.dst2[a] = -1;
+      if (first[a] >= 0) {
+        if (first[a] == 0 ? want_edge : want_planar) g.dst1[a] = tot[first[a]];
+        tot[first[a]] += k.n[a];
+      }
+      if (global) g.dst2[a] = tot[2];
+      tot[2] += k.n[a];
+    }
+  }
+  return kfs;
+}
+
+// Upload the descriptor and chunk tables and run k_global_assemble: one block per <= 1024 points.
+int32_t gm_assemble(llsr_map* m, const std::vector<GmKf>& kfs, float4* edge, float4* planar, float4* global,
+                    hipStream_t s) {
+  std::vector<GmChunk> ch;
+  for (size_t i = 0; i < kfs.size(); ++i)
+    for (int a = 0; a < 3; ++a) {
+      if (kfs[i].dst1[a] < 0 && kfs[i].dst2[a] < 0) continue;
+      for (int b = 0; b < kfs[i].n[a]; b += kGmChunk)
+        ch.push_back({(int)i, a, b, std::min(kGmChunk, kfs[i].n[a] - b)});
+    }
+  if (ch.empty()) return LLSR_OK;
+  const size_t o_ch = align256(kfs.size() * sizeof(GmKf)), bytes = o_ch + ch.size() * sizeof(GmChunk);
+  MAP_OK(m, host_grow(m->hstage, m->cap_hstage, bytes));
+  MAP_OK(m, grow(m->dxf, m->cap_dxf, bytes));
+  std::memcpy(m->hstage, kfs.data(), kfs.size() * sizeof(GmKf));
+  std::memcpy(m->hstage + o_ch, ch.data(), ch.size() * sizeof(GmChunk));
+  MAP_OK(m, hipMemcpyAsync(m->dxf, m->hstage, bytes, hipMemcpyHostToDevice, s));
+  k_global_assemble<<<(unsigned)ch.size(), 256, 0, s>>>(reinterpret_cast<const GmChunk*>(m->dxf + o_ch),
+                                                        reinterpret_cast<const GmKf*>(m->dxf), m->store, edge, planar,
+                                                        global);
+  MAP_OK(m, hipGetLastError());
+  return LLSR_OK;
+}
+
+// VoxelGrid of mapbuf[0, n) at `leaf` into d_out when it holds n points, else into dsbuf and, once
+// the size is known, on into d_out (LLSR_ERANGE when it does not fit; d_out NULL: count only).
+int32_t gm_voxel(llsr_map* m, long long n, float leaf, float4* d_out, int64_t cap, int64_t* n_out, int32_t* pass,
+                 hipStream_t s) {
+  float4* out = d_out;
+  if (!d_out || cap < n) {
+    MAP_OK(m, grow(m->dsbuf, m->cap_ds, (size_t)n));
+    out = m->dsbuf;
+  }
+  const std::vector<VgCloud> one = {{m->mapbuf, n, leaf}};
+  long long o[2];
+  const int32_t rc = vg_run(m, one, out, o, s);
+  if (rc != LLSR_OK) return rc;
+  *n_out = o[1];
+  if (pass && n > 0) {
+    VgPar q;
+    MAP_OK(m, hipMemcpy(&q, m->par, sizeof q, hipMemcpyDeviceToHost));
+    *pass = q.pass;
+  }
+  if (d_out && out != d_out) {
+    if (cap < o[1]) return mfail(m, LLSR_ERANGE, "global map: the downsampled cloud exceeds the output capacity");
+    if (o[1]) MAP_OK(m, hipMemcpyAsync(d_out, out, o[1] * sizeof(float4), hipMemcpyDeviceToDevice, s));
+  }
+  return LLSR_OK;
+}
+
+bool bad_out(const float* p, int64_t cap) { return cap < 0 || (!p && cap != 0); }
+
+}  // namespace
+
+extern "C" int32_t llsr_map_global(llsr_map* m, const llsr_global_map_config* cfg, const float robot_pos[3],
+                                   float* d_global, int64_t cap_global, float* d_edge, int64_t cap_edge,
+                                   float* d_planar, int64_t cap_planar, llsr_global_map_report* rep,
+                                   void* hip_stream) {
+  if (!m || !robot_pos || !rep || bad_out(d_global, cap_global) || bad_out(d_edge, cap_edge) ||
+      bad_out(d_planar, cap_planar))
+    return mfail(m, LLSR_EINVAL, "global map: bad arguments (a NULL output takes capacity 0)");
+  const auto t0 = std::chrono::steady_clock::now();
+  llsr_global_map_config c;
+  if (cfg) c = *cfg;
+  else llsr_global_map_config_default(&c);
+  std::memset(rep, 0, sizeof *rep);
+  rep->call = m->gm_calls;
+  MAP_OK(m, hipSetDevice(m->device));
+  const hipStream_t s = pick(m, hip_stream);
+  const int K = (int)m->kf.size();
+  if (K == 0) return LLSR_OK;  // MO:780: returns before the pointers are touched
+  // step 2: the sorted radius search over cloudKeyPoses3D
+  std::vector<float> p4(4 * (size_t)K);
+  for (int k = 0; k < K; ++k) {
+    for (int a = 0; a < 3; ++a) p4[4 * (size_t)k + a] = m->kf[k].pose[a];
+    p4[4 * (size_t)k + 3] = (float)k;  // intensity = the key index (MO:1695-1697)
+  }
+  std::vector<int32_t> near(K);
+  const int n = llsr_keypose_radius_sorted(p4.data(), K, robot_pos, c.search_radius, near.data());
+  rep->n_in_radius = n;
+  // steps 3 / 5: the filters write into a cloud nobody reads on the first call (MO:807, 836)
+  const bool ds = !c.high_dense && (m->gm_calls >= 1 || !c.first_call_raw);
+  rep->downsampled_poses = rep->downsampled_cloud = ds ? 1 : 0;
+  std::vector<int> list(near.begin(), near.begin() + n);
+  if (ds && n > 0) {
+    MAP_OK(m, grow(m->poses, m->cap_poses, 2 * (size_t)n));
+    MAP_OK(m, host_grow(m->hstage, m->cap_hstage, 2 * (size_t)n * sizeof(float4)));
+    float4* hp = reinterpret_cast<float4*>(m->hstage);
+    for (int i = 0; i < n; ++i) std::memcpy(&hp[i], &p4[4 * (size_t)near[i]], sizeof(float4));
+    MAP_OK(m, hipMemcpyAsync(m->poses, hp, n * sizeof(float4), hipMemcpyHostToDevice, s));
+    const std::vector<VgCloud> pc = {{m->poses, n, c.keypose_leaf}};
+    long long po[2];
+    const int32_t rc = vg_run(m, pc, m->poses + n, po, s);
+    if (rc != LLSR_OK) return rc;
+    MAP_OK(m, hipMemcpyAsync(hp + n, m->poses + n, po[1] * sizeof(float4), hipMemcpyDeviceToHost, s));
+    MAP_OK(m, hipStreamSynchronize(s));
+    list.resize((size_t)po[1]);
+    for (long long q = 0; q < po[1]; ++q) list[q] = (int)hp[n + q].w;  // thisKeyInd (MO:810)
+  }
+  for (int id : list)
+    if (id < 0 || id >= K) return mfail(m, LLSR_ERANGE, "global map: key pose index out of range");
+  // step 4: sizes, then the assembly
+  const int first[3] = {0, 1, -1};
+  long long tot[3];
+  float4* ge = reinterpret_cast<float4*>(d_edge);
+  float4* gp = reinterpret_cast<float4*>(d_planar);
+  float4* gg = reinterpret_cast<float4*>(d_global);
+  std::vector<GmKf> kfs = gm_table(m, list, first, ge != nullptr, gp != nullptr, ds || gg, tot);
+  rep->n_poses_used = (int32_t)list.size();
+  rep->n_edge = tot[0];
+  rep->n_planar = tot[1];
+  rep->n_global_raw = rep->n_global = tot[2];  // n_global: an upper bound until the VoxelGrid ran
+  if ((ge && cap_edge < tot[0]) || (gp && cap_planar < tot[1]) || (gg && !ds && cap_global < tot[2]))
+    return mfail(m, LLSR_ERANGE, "global map: a cloud exceeds its output capacity");
+  if (ds && tot[2] >= (long long)INT32_MAX)
+    return mfail(m, LLSR_ERANGE, "global map: more than LLSR_VOXEL_GRID_MAX_POINTS points to downsample");
+  if (ds) MAP_OK(m, grow(m->mapbuf, m->cap_map, (size_t)tot[2]));
+  int32_t rc = gm_assemble(m, kfs, ge, gp, ds ? m->mapbuf : gg, s);
+  if (rc != LLSR_OK) return rc;
+  if (ds) {
+    rc = gm_voxel(m, tot[2], c.cloud_leaf, gg, cap_global, &rep->n_global, &rep->passthrough, s);
+    if (rc != LLSR_OK) return rc;
+  }
+  MAP_OK(m, hipStreamSynchronize(s));
+  rep->call = ++m->gm_calls;
+  rep->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_map_save(llsr_map* m, float* d_corner, int64_t cap_corner, float* d_surf, int64_t cap_surf,
+                                 int64_t* n_corner, int64_t* n_surf, void* hip_stream) {
+  if (!m || !n_corner || !n_surf || bad_out(d_corner, cap_corner) || bad_out(d_surf, cap_surf))
+    return mfail(m, LLSR_EINVAL, "save map: bad arguments (a NULL output takes capacity 0)");
+  MAP_OK(m, hipSetDevice(m->device));
+  const hipStream_t s = pick(m, hip_stream);
+  // MO:382-395: every keyframe in index order; cornerMap raw, surfaceMap = surf + outlier per
+  // keyframe through downSizeFilterSurf
+  std::vector<int> list(m->kf.size());
+  for (size_t k = 0; k < list.size(); ++k) list[k] = (int)k;
+  const int first[3] = {0, 1, 1};
+  long long tot[3];
+  float4* gc = reinterpret_cast<float4*>(d_corner);
+  std::vector<GmKf> kfs = gm_table(m, list, first, gc != nullptr, true, false, tot);
+  *n_corner = tot[0];
+  *n_surf = tot[1];  // an upper bound until the VoxelGrid ran
+  if (gc && cap_corner < tot[0]) return mfail(m, LLSR_ERANGE, "save map: the corner map exceeds its output capacity");
+  if (tot[1] >= (long long)INT32_MAX)
+    return mfail(m, LLSR_ERANGE, "save map: more than LLSR_VOXEL_GRID_MAX_POINTS points to downsample");
+  MAP_OK(m, grow(m->mapbuf, m->cap_map, (size_t)tot[1]));
+  int32_t rc = gm_assemble(m, kfs, gc, m->mapbuf, nullptr, s);
+  if (rc != LLSR_OK) return rc;
+  rc = gm_voxel(m, tot[1], m->cfg.surf_leaf, reinterpret_cast<float4*>(d_surf), cap_surf, n_surf, nullptr, s);
+  if (rc != LLSR_OK) return rc;
+  MAP_OK(m, hipStreamSynchronize(s));
+  return LLSR_OK;
 }

@@ -46,6 +46,8 @@ EXPORTS = [
     "llsr_pose_to_odometry", "llsr_odometry_to_transform", "llsr_fusion_laser_odometry", "llsr_fusion_aft_mapped",
     "llsr_integrate_transformation", "llsr_transform_to_end", "llsr_odom_init", "llsr_odom_callback",
     "llsr_update_initial_guess", "llsr_odometry_batch_odom", "llsr_odometry_fetch_lm", "llsr_mapping_batch_odom",
+    "llsr_global_map_config_default", "llsr_map_global", "llsr_map_save", "llsr_keypose_radius_sorted",
+    "llsr_mapping_global_map", "llsr_mapping_save_map",
 ]
 
 
@@ -138,6 +140,14 @@ def lib():
         L.llsr_map_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                        C.POINTER(_abi.MapReport), C.c_void_p]
         L.llsr_map_keyframe_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.llsr_global_map_config_default.argtypes = [C.POINTER(_abi.GlobalMapConfig)]
+        _gm_out = [C.c_void_p, C.c_int64] * 3 + [C.POINTER(_abi.GlobalMapReport), C.c_void_p]
+        L.llsr_map_global.argtypes = [C.c_void_p, C.POINTER(_abi.GlobalMapConfig), C.c_void_p] + _gm_out
+        L.llsr_mapping_global_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.GlobalMapConfig)] + _gm_out
+        _save = [C.c_void_p, C.c_int64] * 2 + [C.POINTER(C.c_int64)] * 2 + [C.c_void_p]
+        L.llsr_map_save.argtypes = [C.c_void_p] + _save
+        L.llsr_mapping_save_map.argtypes = [C.c_void_p, C.c_int32] + _save
+        L.llsr_keypose_radius_sorted.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p]
         L.llsr_mapping_init.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.MapConfig)]
         L.llsr_mapping_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.llsr_mapping_fetch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.MappingSlot)]
@@ -182,6 +192,8 @@ class Pipeline:
         H, W = cfg.num_vertical_scans, cfg.num_horizontal_scans
         self.max_points = max_points or 2 * H * W
         self.max_batch = max_batch
+        self.device = device
+        self._gm_caps = {}  # mapping_global_map's output capacities per slot
         h = C.c_void_p()
         rc = lib().llsr_create(C.byref(cfg), device, max_batch, self.max_points, C.byref(h))
         if rc != 0:
@@ -449,6 +461,26 @@ class Pipeline:
     def mapping_reset(self):
         self._check(lib().llsr_mapping_reset(self._h), "llsr_mapping_reset")
 
+    def mapping_global_map(self, b: int, cfg: _abi.GlobalMapConfig | None = None, edge: bool = True,
+                           planar: bool = True, stream: int = 0) -> dict:
+        """publishGlobalMap on slot b's keyframes (llsr_mapping_global_map), around the slot's
+        transformAftMapped position: as LocalMap.global_map."""
+        import torch
+        caps = self._gm_caps.setdefault(b, [1, 1, 1])
+        call = lambda *out: lib().llsr_mapping_global_map(  # noqa: E731
+            self._h, b, C.byref(cfg) if cfg is not None else None, *out, C.c_void_p(stream))
+        r = _global_map(torch, torch.device("cuda", self.device), call, caps, edge, planar)
+        self._check(r.pop("rc"), "llsr_mapping_global_map")
+        return r
+
+    def mapping_save_map(self, b: int, stream: int = 0):
+        """saveMapService's (cornerMap, surfaceMap) of slot b (llsr_mapping_save_map)."""
+        import torch
+        call = lambda *out: lib().llsr_mapping_save_map(self._h, b, *out, C.c_void_p(stream))  # noqa: E731
+        rc, c, su = _save_map(torch, torch.device("cuda", self.device), call)
+        self._check(rc, "llsr_mapping_save_map")
+        return c, su
+
 
 def mapping_associate(transform_sum_fa, bef, aft):
     """Host-only pose glue of the mapping chain (llsr_mapping_associate): OdometryToTransform then
@@ -660,6 +692,65 @@ def map_config(lidar: str | None = None, **kw) -> _abi.MapConfig:
     return c
 
 
+def global_map_config(**kw) -> _abi.GlobalMapConfig:
+    """llsr_global_map_config_default (radius 5000, leaves 1.0 / 0.4, the reference's first-call
+    behaviour), then the overrides."""
+    c = _abi.GlobalMapConfig()
+    if lib().llsr_global_map_config_default(C.byref(c)) != 0:
+        raise LlsrError("llsr_global_map_config_default failed")
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def keypose_radius_sorted(poses4, pos, radius: float) -> np.ndarray:
+    """publishGlobalMap's sorted radius search (llsr_keypose_radius_sorted, host only): indices of
+    the key poses with d^2 < float(radius^2) by ascending d^2, equal d^2 by ascending index."""
+    p = np.ascontiguousarray(poses4, np.float32).reshape(-1, 4)
+    q = np.ascontiguousarray(pos, np.float32)
+    out = np.zeros(max(len(p), 1), np.int32)
+    n = lib().llsr_keypose_radius_sorted(p.ctypes.data, len(p), q.ctypes.data, radius, out.ctypes.data)
+    if n < 0:
+        raise LlsrError(f"llsr_keypose_radius_sorted: {n}")
+    return out[:n].copy()
+
+
+def _global_map(torch, device, call, caps, edge: bool, planar: bool) -> dict:
+    """Run a llsr_map_global-shaped call with output buffers of caps[global, edge, planar] points,
+    growing them once to the reported sizes on LLSR_ERANGE."""
+    rep = _abi.GlobalMapReport()
+    want = (True, edge, planar)
+    for _ in range(2):
+        bufs = [torch.empty((max(c, 1), 4), dtype=torch.float32, device=device) if w else None
+                for c, w in zip(caps, want)]
+        args = []
+        for b in bufs:
+            args += [C.c_void_p(b.data_ptr()), b.shape[0]] if b is not None else [None, 0]
+        rc = call(*args, C.byref(rep))
+        if rc != _abi.LLSR_ERANGE:
+            break
+        for k, n in enumerate((rep.n_global, rep.n_edge, rep.n_planar)):
+            caps[k] = max(caps[k], int(n))
+    r = {"rc": rc, "report": rep.as_dict(), "global": None, "edge": None, "planar": None}
+    if rc == 0:
+        for key, b, n in zip(("global", "edge", "planar"), bufs, (rep.n_global, rep.n_edge, rep.n_planar)):
+            r[key] = b[:n] if b is not None else None
+    return r
+
+
+def _save_map(torch, device, call):
+    """Run a llsr_map_save-shaped call, growing the two buffers once to the reported sizes."""
+    nc, ns = C.c_int64(0), C.c_int64(0)
+    caps = [1, 1]
+    for _ in range(2):
+        c, s = (torch.empty((cap, 4), dtype=torch.float32, device=device) for cap in caps)
+        rc = call(C.c_void_p(c.data_ptr()), caps[0], C.c_void_p(s.data_ptr()), caps[1], C.byref(nc), C.byref(ns))
+        if rc != _abi.LLSR_ERANGE:
+            break
+        caps = [max(1, nc.value), max(1, ns.value)]
+    return rc, c[:nc.value], s[:ns.value]
+
+
 class LocalMap:
     """MapOptimization's keyframe store + local map on a HIP device (llsr_map, include/llsr.h):
     saveKeyFramesAndFactor's clouds (MO:1686-1752), extractSurroundingKeyFrames (MO:1096-1232),
@@ -680,6 +771,7 @@ class LocalMap:
         self._s = torch.cuda.Stream(device=self.device)
         self._n_corner = 0
         self._n_surf = 0
+        self._gm_caps = [1, 1, 1]  # global_map's output capacities (global, edge, planar), grown on demand
 
     def close(self):
         if getattr(self, "_m", None):
@@ -775,6 +867,28 @@ class LocalMap:
                                            C.c_void_p(os_.data_ptr()), cs, C.byref(rep), s), "llsr_map_extract")
         self._leave()
         return oc[:rep.n_corner_ds], os_[:rep.n_surf_ds], rep.as_dict()
+
+    def global_map(self, robot_pos, cfg: _abi.GlobalMapConfig | None = None, edge: bool = True,
+                   planar: bool = True) -> dict:
+        """publishGlobalMap (MO:775-892, llsr_map_global): {"global", "edge", "planar"} clouds (edge /
+        planar None when not requested) and "report"."""
+        pos = np.ascontiguousarray(robot_pos, np.float32)
+        s = self._enter()
+        call = lambda *out: lib().llsr_map_global(self._m, C.byref(cfg) if cfg is not None else None,  # noqa: E731
+                                                  pos.ctypes.data, *out, s)
+        r = _global_map(self._torch, self.device, call, self._gm_caps, edge, planar)
+        self._check(r.pop("rc"), "llsr_map_global")
+        self._leave()
+        return r
+
+    def save_map(self):
+        """saveMapService's clouds (MO:382-395, llsr_map_save): (cornerMap, surfaceMap)."""
+        s = self._enter()
+        call = lambda *out: lib().llsr_map_save(self._m, *out, s)  # noqa: E731
+        rc, c, su = _save_map(self._torch, self.device, call)
+        self._check(rc, "llsr_map_save")
+        self._leave()
+        return c, su
 
     def keyframe_ids(self) -> np.ndarray:
         n = lib().llsr_map_keyframe_ids(self._m, None, 0)

@@ -7,6 +7,7 @@ import numpy as np
 
 ABI_VERSION = 2  # LLSR_ABI_VERSION of include/llsr.h these bindings mirror (checked at load)
 LLSR_OK = 0
+LLSR_ERANGE = -34
 LLSR_LIDAR_VLP16 = 0
 LLSR_LIDAR_HDL64E = 2
 LLSR_MODE_FAITHFUL = 0
@@ -262,6 +263,23 @@ class MapReport(C.Structure):
     _fields_ = [("n_in_radius", C.c_int32), ("n_poses_ds", C.c_int32), ("n_keyframes", C.c_int32),
                 ("n_transformed", C.c_int32), ("n_corner_map", C.c_int64), ("n_surf_map", C.c_int64),
                 ("n_corner_ds", C.c_int64), ("n_surf_ds", C.c_int64), ("ms", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class GlobalMapConfig(C.Structure):
+    """llsr_global_map_config (include/llsr.h): publishGlobalMap's parameters."""
+    _fields_ = [("search_radius", C.c_float), ("keypose_leaf", C.c_float), ("cloud_leaf", C.c_float),
+                ("high_dense", C.c_int32), ("first_call_raw", C.c_int32)]
+
+
+class GlobalMapReport(C.Structure):
+    """llsr_global_map_report (include/llsr.h): one publishGlobalMap call."""
+    _fields_ = [("call", C.c_int32), ("n_in_radius", C.c_int32), ("n_poses_used", C.c_int32),
+                ("downsampled_poses", C.c_int32), ("downsampled_cloud", C.c_int32), ("passthrough", C.c_int32),
+                ("n_edge", C.c_int64), ("n_planar", C.c_int64), ("n_global_raw", C.c_int64),
+                ("n_global", C.c_int64), ("ms", C.c_float)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
