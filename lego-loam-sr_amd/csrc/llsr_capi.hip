@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "llsr_handle.h"
+#include "llsr_isort.h"
 #include "llsr_libm.h"
 
 namespace llsr {
@@ -25,17 +26,19 @@ template <bool kLds> __global__ void k_label(DevCfg, DevBufs);
 __global__ void k_segment(DevCfg, const float4*, const int64_t*, DevBufs);
 void launch_fa_points(const DevCfg&, const DevBufs&, int, hipStream_t);
 __global__ void k_select_ring(DevCfg, DevBufs);
-__global__ void k_vox_pcl(DevCfg, DevBufs);
+__global__ void k_vox_top(DevCfg, DevBufs, VoxRanges);
+__global__ void k_vox_leaf(DevCfg, DevBufs, VoxRanges);
+__global__ void k_vox_sum(DevCfg, DevBufs);
 __global__ void k_debug_exact_sort(const float*, int, int*, long long*);
-__global__ void k_debug_exact_sort32(const uint32_t*, int, int*);
 __global__ void k_debug_half_passed(const float*, int, uint8_t*);
 __global__ void k_fa_concat(DevCfg, DevBufs);
 __global__ void k_dbscan_adj(DevCfg, DevBufs, const float4* __restrict__);
 __global__ void k_vis_clouds(DevCfg, DevBufs, int, float4*, int*);
 template <int kDbL> __global__ void k_dbscan_merge(DevCfg, DevBufs);
 
-__global__ void k_init_counts(int* counts, int B) {
+__global__ void k_init_counts(int* counts, int B, int* vox_count) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < kVoxSub) vox_count[b * kVoxCntStride] = 0;  // (the grid has at least 256 threads)
   if (b >= B) return;
   int* c = counts + b * kCnt;
   for (int k = 0; k < kCnt; ++k) c[k] = 0;
@@ -66,10 +69,29 @@ static bool use_fused(const llsr_handle* h) { return h->dc.ccl_lds != 0; }
 // 0.180 -> 0.167 ms per 1024 scans), 1024 for the larger ones (HDL-64E: 512 was slower)
 static int per_scan_threads(const DevCfg& c) { return c.ccl_lds ? 512 : 1024; }
 
-// the PCL-order less-flat VoxelGrid of every pending ring
-static void launch_vox_pcl(const DevCfg& c, const DevBufs& d, int B, hipStream_t s) {
-  k_vox_pcl<<<dim3(c.H, B), 256, 0, s>>>(c, d);
+// the PCL-order less-flat VoxelGrid of every pending ring (the profiling ring's k_vox_pcl slot):
+// block-wide partitions, the listed ranges as one pool of one-wave items, the centroids. vr's
+// counters are zero before (k_init_counts). `waves`: k_vox_leaf's largest grid (vox_leaf_waves); a
+// ring lists ~6 ranges, so small batches launch a smaller one. Diagnostics: dbg_phase 100 stops after k_vox_top, 101 and 102
+// after k_vox_leaf.
+static void launch_vox_pcl(const DevCfg& c, const DevBufs& d, const VoxRanges& vr, int waves, int B, hipStream_t s) {
+  k_vox_top<<<dim3(c.H, B), 256, 0, s>>>(c, d, vr);
+  if (c.dbg_phase <= 100) return;
+  k_vox_leaf<<<std::min(waves, (8 * c.H * B + kVoxSub - 1) / kVoxSub * kVoxSub), 64, 0, s>>>(c, d, vr);
+  if (c.dbg_phase <= 102) return;
+  k_vox_sum<<<dim3(c.H, B), 256, 0, s>>>(c, d);
 }
+// k_vox_leaf's largest grid, a multiple of kVoxSub: 16 times the device's wave slots (32 per CU at
+// the kernel's 8 waves per SIMD). The items' costs differ widely; with one wave per slot each
+// keeps its fixed share of them and the kernel waits for the unluckiest (0.77 ms per 1024 VLP-16
+// scans at 8 times the slots against 1.09 at one; 16 and 32 times are equal within noise), with
+// more workgroups than slots the dispatcher hands the next few items to whichever slot is free.
+static int vox_leaf_waves(int device) {
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
+  return std::max(kVoxSub, 16 * 32 * cus / kVoxSub * kVoxSub);
+}
+static const size_t kVoxCntBytes = sizeof(int) * kVoxSub * kVoxCntStride;
 
 extern "C" int32_t llsr_abi_version(void) { return LLSR_ABI_VERSION; }
 
@@ -174,6 +196,16 @@ extern "C" int32_t llsr_create(const llsr_config* cfg, int32_t hip_device, int32
         llsr_host::feature_layout(cv, h->d, max_batch, c.H, c.HW, kCnt, kAdjCap * kAdjWords);
       }) != hipSuccess)
     return LLSR_ENOMEM;
+  {  // the VoxelGrid sort's range list (llsr_device.h VoxRanges) and, behind it, its counters
+    const size_t subcap = ((size_t)max_batch * c.H + kVoxSub - 1) / kVoxSub * kBsList;
+    if (subcap > (size_t)INT_MAX ||
+        llsr_host::alloc(h->vox_mem, sizeof(int2) * subcap * kVoxSub + kVoxCntBytes) != hipSuccess)
+      return LLSR_ENOMEM;
+    h->vox.item = static_cast<int2*>(h->vox_mem.get());
+    h->vox.count = reinterpret_cast<int*>(h->vox.item + subcap * kVoxSub);
+    h->vox.subcap = (int)subcap;
+    h->vox_waves = vox_leaf_waves(hip_device);
+  }
   {
     uint32_t mt0[624];
     mt_first_state(mt0);
@@ -346,7 +378,7 @@ extern "C" int32_t llsr_process_batch(llsr_handle* h, const float* d_xyzi, const
   mark();
   const bool fused = use_fused(h);
   if (!fused) HIP_OK(h, hipMemsetAsync(h->d.ccl_a, 0xFF, sizeof(int) * (size_t)B * c.HW, s));
-  k_init_counts<<<(B + 255) / 256, 256, 0, s>>>(h->d.counts, B);
+  k_init_counts<<<(B + 255) / 256, 256, 0, s>>>(h->d.counts, B, h->vox.count);
   mark();
   if (fused) {  // fused projection + column ground pass with the cell table in LDS
     k_project_fused<<<B, 1024, fused_lds(c), s>>>(c, pts, d_offsets, h->d);
@@ -375,7 +407,7 @@ extern "C" int32_t llsr_process_batch(llsr_handle* h, const float* d_xyzi, const
   mark();
   k_select_ring<<<dim3(c.H, B), 256, 0, s>>>(c, h->d);
   mark();
-  if (c.exact_vg) launch_vox_pcl(c, h->d, B, s);  // the PCL-order VoxelGrid
+  if (c.exact_vg) launch_vox_pcl(c, h->d, h->vox, h->vox_waves, B, s);
   mark();
   k_fa_concat<<<B, 256, 0, s>>>(c, h->d);
   mark();
@@ -433,22 +465,44 @@ extern "C" int32_t llsr_debug_exact_sort(const float* vals, int32_t n, int32_t* 
 }
 
 // Diagnostics (not part of the ABI header): the PCL-order VoxelGrid's exact sort of 32-bit keys
-// (VoxLess32: voxel rank << 11 | position) on n <= 2048 host ranks < 2^21, as k_vox_pcl runs it
-// (block_introsort); out[k] = the input position at sorted position k. For
-// tests/test_gpu_features_ties.py.
+// (VoxLess32: voxel rank << 11 | position) on n <= 2048 host ranks < 2^21, by the kernels a batch
+// runs (k_vox_top, k_vox_leaf) on a one-ring scan made of the keys; out[k] = the input position at
+// sorted position k. For tests/test_gpu_features_ties.py and tests/test_gpu_vox_split.py.
 extern "C" int32_t llsr_debug_exact_sort32(const uint32_t* ranks, int32_t n, int32_t* out) {
   if (!ranks || !out || n < 0 || n > 2048) return LLSR_EINVAL;
   for (int32_t t = 0; t < n; ++t)
     if (ranks[t] >= (1u << 21)) return LLSR_EINVAL;
   if (n == 0) return LLSR_OK;
-  llsr_host::DevMem dv, di;
-  if (llsr_host::alloc(dv, sizeof(uint32_t) * n) != hipSuccess || llsr_host::alloc(di, sizeof(int) * n) != hipSuccess)
+  std::vector<uint32_t> key(n);
+  for (int32_t t = 0; t < n; ++t) key[t] = (ranks[t] << 11) | (uint32_t)t;
+  // ring_cnt [3] (the ring pending with n candidates), start_ring [1]; the list (one ring per
+  // sub-list at most) and its counters
+  const int head[4] = {0, 0, -1 - n, 0};
+  int device = 0;
+  llsr_host::DevMem dk, dh, di;
+  if (hipGetDevice(&device) != hipSuccess || llsr_host::alloc(dk, sizeof(uint32_t) * n) != hipSuccess ||
+      llsr_host::alloc(dh, sizeof head) != hipSuccess ||
+      llsr_host::alloc(di, sizeof(int2) * kBsList * kVoxSub + kVoxCntBytes) != hipSuccess)
     return LLSR_ENODEV;
-  if (hipMemcpy(dv, ranks, sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess) return LLSR_EIO;
-  k_debug_exact_sort32<<<1, 256>>>((const uint32_t*)dv.get(), n, (int*)di.get());
-  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpy(out, di, sizeof(int) * n, hipMemcpyDeviceToHost) != hipSuccess)
+  int2* items = static_cast<int2*>(di.get());
+  if (hipMemcpy(dk, key.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(dh, head, sizeof head, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(items + kBsList * kVoxSub, 0, kVoxCntBytes) != hipSuccess)
     return LLSR_EIO;
+  DevCfg c{};
+  c.H = 1;
+  c.W = c.HW = n;
+  c.dbg_phase = 102;  // the sort without the centroids
+  DevBufs d{};
+  d.ccl_a = static_cast<int*>(dk.get());
+  d.ring_cnt = static_cast<int*>(dh.get());
+  d.start_ring = d.ring_cnt + 3;
+  const VoxRanges vr{items, reinterpret_cast<int*>(items + kBsList * kVoxSub), kBsList};
+  launch_vox_pcl(c, d, vr, vox_leaf_waves(device), 1, nullptr);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(key.data(), dk, sizeof(uint32_t) * n, hipMemcpyDeviceToHost) != hipSuccess)
+    return LLSR_EIO;
+  for (int32_t t = 0; t < n; ++t) out[t] = (int32_t)(key[t] & 0x7ffu);
   return LLSR_OK;
 }
 
@@ -516,7 +570,10 @@ static void restore_selection(llsr_handle* h, int B, hipStream_t s) {
   const DevCfg& c = h->dc;
   launch_fa_points(c, h->d, B, s);
   k_select_ring<<<dim3(c.H, B), 256, 0, s>>>(c, h->d);
-  if (c.exact_vg) launch_vox_pcl(c, h->d, B, s);
+  if (c.exact_vg) {
+    (void)hipMemsetAsync(h->vox.count, 0, kVoxCntBytes, s);
+    launch_vox_pcl(c, h->d, h->vox, h->vox_waves, B, s);
+  }
   (void)hipStreamSynchronize(s);
 }
 
@@ -532,13 +589,14 @@ extern "C" float llsr_debug_phase_ms(llsr_handle* h, int32_t k, int32_t phase, i
   const int B = h->last_B;
   hipEvent_t e0 = h->ev[0][0], e1 = h->ev[0][1];
   if (sync_last(h) != LLSR_OK) return -1.f;
-  if (k == 9) {  // k_vox_pcl needs the keys k_select_ring leaves: both re-run before each launch
-    float tot = 0.f;
+  if (k == 9) {  // the PCL-order VoxelGrid needs the keys k_select_ring leaves and an empty range
+    float tot = 0.f;  // list: both redone before each launch
     for (int r = 0; r < reps; ++r) {
       launch_fa_points(h->dc, h->d, B, s);
       k_select_ring<<<dim3(c.H, B), 256, 0, s>>>(h->dc, h->d);
+      (void)hipMemsetAsync(h->vox.count, 0, kVoxCntBytes, s);
       (void)hipEventRecord(e0, s);
-      launch_vox_pcl(c, h->d, B, s);
+      launch_vox_pcl(c, h->d, h->vox, h->vox_waves, B, s);
       (void)hipEventRecord(e1, s);
       float ms = 0.f;
       if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return -1.f;

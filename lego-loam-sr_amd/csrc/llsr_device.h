@@ -89,6 +89,24 @@ struct DevBufs {
                         // last S; HW after llsr_reset_state), so a batch clears only [S, seg_zero)
 };
 
+// The work items of the PCL-order VoxelGrid's sort (k_vox_top -> k_vox_leaf), owned by the handle:
+// an item = (first | last << 12 | depth limit << 24 of a range of a ring's keys, scan * H + ring).
+// One counter for a whole batch serialises its atomics (~20 ns each on one address: as long as
+// k_vox_top's own work), so the list is kVoxSub sub-lists, each with a counter on a cache line of
+// its own; ring slot s appends to sub-list vox_sub(s), its whole count with one atomicAdd.
+// Sub-list j: item[j * subcap, +count[j * kVoxCntStride]). Any kVoxSub consecutive slots map to
+// kVoxSub different sub-lists and a ring lists fewer than kBsList ranges (llsr_isort.h), so
+// subcap = ceil(max_batch * H / kVoxSub) * kBsList holds any batch. The counters are zeroed by the
+// batch's init kernel.
+constexpr int kVoxSub = 64;
+constexpr int kVoxCntStride = 32;  // ints: 128 B
+struct VoxRanges {
+  int2* item;
+  int* count;
+  int subcap;
+};
+__host__ __device__ __forceinline__ int vox_sub(int slot) { return (slot + slot / kVoxSub) % kVoxSub; }
+
 // C_HALF before k_fa_points when k_segment's first tile of cells holds no passing point
 constexpr int kHalfUnknown = -2;
 

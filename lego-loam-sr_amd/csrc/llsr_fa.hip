@@ -330,19 +330,6 @@ __global__ __launch_bounds__(256) void k_debug_exact_sort(const float* vals, int
   for (int t = threadIdx.x; t < n; t += 256) out[t] = (int)(uint32_t)key[t];
 }
 
-// Diagnostics (llsr_debug_exact_sort32): the PCL-order VoxelGrid's sort on 32-bit keys (rank << 11 |
-// position, VoxLess32) of n <= kRingMax ranks < 2^21, as k_vox_pcl runs it (block_introsort, 256
-// threads); out receives the original positions in sorted order.
-__global__ __launch_bounds__(256) void k_debug_exact_sort32(const uint32_t* ranks, int n, int* out) {
-  __shared__ uint32_t key[kRingMax];
-  __shared__ uint16_t Lp[kRingMax], Rp[kRingMax];
-  __shared__ BlockSortLds bsl;
-  for (int t = threadIdx.x; t < n; t += 256) key[t] = (ranks[t] << 11) | (uint32_t)t;
-  block_introsort<256>(key, n, Lp, Rp, bsl, VoxLess32{});
-  __syncthreads();
-  for (int t = threadIdx.x; t < n; t += 256) out[t] = (int)(key[t] & 0x7ffu);
-}
-
 // Serial greedy pick (FA:1175-1259) over a candidate list already in visiting order, by one wave:
 // each chunk of 64 candidates reads `picked` once; the first still-alive candidate is selected,
 // candidates inside its suppression interval die, repeat. Steps per chunk = picks in the chunk.
@@ -761,9 +748,9 @@ __global__ __launch_bounds__(256, 5) void k_select_ring(DevCfg c, DevBufs d) {
   };
   if (c.exact_vg) {
     // LLSR_VOXEL_ORDER_PCL (llsr_set_voxel_order): std::sort(index_vector) by voxel id alone (PCL
-    // 1.10 voxel_grid.hpp) and the centroids summed in that order run in k_vox_pcl, a kernel of
-    // its own with a small LDS footprint (more rings per CU for the sort's dependent chains). It
-    // sorts 32-bit keys (rank << 11 | candidate): each voxel id replaced by its dense rank among the
+    // 1.10 voxel_grid.hpp) and the centroids summed in that order run in kernels of their own
+    // (k_vox_top / k_vox_leaf / k_vox_sum below). They
+    // sort 32-bit keys (rank << 11 | candidate): each voxel id replaced by its dense rank among the
     // ring's ids, which keeps the outcome of every comparison; the ranks come from the sorted voxel
     // runs. The keys and the candidate positions go to the scratch slots of the ring's positions
     // (ccl_a / ccl_b, dead since k_label), and rc[2H + i] = -1 - L marks the ring pending.
@@ -847,16 +834,103 @@ __global__ __launch_bounds__(256, 5) void k_select_ring(DevCfg c, DevBufs d) {
 
 // ---------------------------------------------------------------------------------------------
 // K8b the less-flat VoxelGrid in PCL order (LLSR_VOXEL_ORDER_PCL; FA:1268-1271, PCL 1.10
-// VoxelGrid::applyFilter): each pending ring's (voxel id << 32 | candidate) keys sorted by voxel id
-// exactly as libstdc++'s std::sort leaves them (block_introsort, llsr_isort.h), then one lane per
-// voxel sums its points in that order. Split from k_select_ring so the sort runs at 8 workgroups
-// per CU (32-bit keys: 17 KB LDS, <= 64 VGPRs) instead of 5: its chains of dependent LDS steps
-// want rings in flight. grid (H, B), block 256.
+// VoxelGrid::applyFilter): each pending ring's (voxel rank << 11 | candidate) keys sorted by voxel
+// rank exactly as libstdc++'s std::sort leaves them (llsr_isort.h), then one lane per voxel sums its
+// points in that order. Three launches on one stream, the keys in the ring's scratch slot between
+// them: k_vox_top partitions a ring block-wide while its ranges are above kBsBig and lists the
+// ranges that remain; k_vox_leaf finishes every listed range with one wave, the ranges of all rings
+// and scans as one pool of work items (a ring's few ranges differ widely in cost, so waves tied
+// to one ring wait for its longest); k_vox_sum builds the centroids.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 8) void k_vox_pcl(DevCfg c, DevBufs d) {
+__device__ __forceinline__ uint32_t* vox_keys(const DevCfg& c, const DevBufs& d, int slot) {
+  return reinterpret_cast<uint32_t*>(d.ccl_a + (size_t)(slot / c.H) * c.HW) + d.start_ring[slot];
+}
+
+// grid (H, B), block 256. A ring of at most kBsBig candidates is one range as it stands.
+__global__ __launch_bounds__(256, 8) void k_vox_top(DevCfg c, DevBufs d, VoxRanges vr) {
   __shared__ uint32_t key[kRingMax];
   __shared__ uint16_t Lp[kRingMax], Rp[kRingMax];
   __shared__ BlockSortLds bsl;
+  const int i = blockIdx.x, b = blockIdx.y, H = c.H, slot = b * H + i;
+  const int r = d.ring_cnt[(size_t)b * 3 * H + 2 * H + i];
+  if (r >= -2) return;  // not pending (no candidates, or written by k_select_ring), or one candidate
+  const int L = -1 - r;
+  const int tid = threadIdx.x, w = tid >> 6, l = lane_id();
+  int* cnt = vr.count + vox_sub(slot) * kVoxCntStride;
+  int2* sub = vr.item + (size_t)vox_sub(slot) * vr.subcap;
+  if (L <= kBsBig) {
+    if (tid == 0) {
+      const int q = atomicAdd(cnt, 1);
+      if (q < vr.subcap) sub[q] = make_int2(bs_enc(0, L, 2 * (31 - __clz(L))), slot);
+    }
+    return;
+  }
+  for (int t = tid; t < L; t += 256) key[t] = vox_keys(c, d, slot)[t];
+  __syncthreads();
+  const VoxLess32 lt{};
+  const int nr = block_top_ranges<256>(key, L, Lp, Rp, bsl, lt);
+  // a listed range above kBsBig (its depth limit spent, or the list nearly full: rare) does not fit
+  // a leaf item: a wave of this workgroup finishes it here
+  {
+    SmallWindow win;
+    SortClocks ck;
+    int nbig = 0;
+    for (int k = 0; k < nr; ++k) {
+      const int it = bsl.rng[k];
+      if (bs_last(it) - bs_first(it) <= kBsBig || (nbig++ & 3) != w) continue;
+      wave_finish_range(key, Lp, Rp, bsl.stk[w], bs_first(it), bs_last(it), bs_depth(it), win, ck, lt);
+    }
+    win.flush(key, Lp, Rp, lt);
+  }
+  __syncthreads();
+  for (int t = tid; t < L; t += 256) vox_keys(c, d, slot)[t] = key[t];
+  if (w == 0) {  // the ring's items with one atomic (nr < kBsList = 64: one lane per range)
+    const int it = l < nr ? bsl.rng[l] : 0;
+    const int len = bs_last(it) - bs_first(it);
+    const bool keep = len >= 2 && len <= kBsBig;
+    const unsigned long long m = ballot(keep);
+    int q0 = 0;
+    if (l == 0 && m) q0 = atomicAdd(cnt, (int)__popcll(m));
+    const int q = __builtin_amdgcn_readfirstlane(q0) + lane_rank(m);
+    if (keep && q < vr.subcap) sub[q] = make_int2(it, slot);
+  }
+}
+
+// One wave per workgroup; a fixed grid (a multiple of kVoxSub, several times the device's wave
+// slots: launch_vox_pcl): workgroup w takes the items w / kVoxSub, + gridDim.x / kVoxSub, ... of
+// sub-list w % kVoxSub.
+// A range is loaded to LDS (4.3 KB: eight workgroups per SIMD), finished as a wave of
+// block_introsort finishes a dealt range, and stored back in place.
+__global__ __launch_bounds__(64, 8) void k_vox_leaf(DevCfg c, DevBufs d, VoxRanges vr) {
+  __shared__ uint32_t key[kBsBig];
+  __shared__ uint16_t Lp[kBsBig], Rp[kBsBig];
+  __shared__ int stk[kBsStack];
+  const int l = lane_id();
+  const int j = blockIdx.x % kVoxSub;
+  const int cnt = min(vr.count[j * kVoxCntStride], vr.subcap);
+  const int2* sub = vr.item + (size_t)j * vr.subcap;
+  const VoxLess32 lt{};
+  for (int q = blockIdx.x / kVoxSub; q < cnt; q += gridDim.x / kVoxSub) {
+    const int2 e = sub[q];
+    const int it = __builtin_amdgcn_readfirstlane(e.x), slot = __builtin_amdgcn_readfirstlane(e.y);
+    const int n = bs_last(it) - bs_first(it);
+    uint32_t* gk = vox_keys(c, d, slot) + bs_first(it);
+    for (int t = l; t < n; t += 64) key[t] = gk[t];
+    wave_sync_lds();
+    SmallWindow win;
+    SortClocks ck;
+    wave_finish_range(key, Lp, Rp, stk, 0, n, bs_depth(it), win, ck, lt);
+    win.flush(key, Lp, Rp, lt);
+    for (int t = l; t < n; t += 64) gk[t] = key[t];
+    wave_sync_lds();
+  }
+}
+
+// grid (H, B), block 256: the centroids of a pending ring from its sorted keys; publishes the
+// ring's less-flat count.
+__global__ __launch_bounds__(256, 8) void k_vox_sum(DevCfg c, DevBufs d) {
+  __shared__ uint32_t key[kRingMax];
+  __shared__ uint16_t cpos[kRingMax];
   constexpr int kLp = kRingMax / 256;
   __shared__ int scnt[kLp * 4 + 1];
   const int i = blockIdx.x, b = blockIdx.y, H = c.H;
@@ -867,15 +941,13 @@ __global__ __launch_bounds__(256, 8) void k_vox_pcl(DevCfg c, DevBufs d) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const int sp = d.start_ring[b * H + i];
   const size_t base = (size_t)b * c.HW;
-  const uint32_t* gk = reinterpret_cast<const uint32_t*>(d.ccl_a + base) + sp;
+  const uint32_t* gk = vox_keys(c, d, b * H + i);
   const uint16_t* gc = reinterpret_cast<const uint16_t*>(d.ccl_b + base) + sp;
-  for (int t = tid; t < L; t += nt) key[t] = gk[t];
-  // barriers on entry and exit (diagnostic phases 100 / 101 / 102: the block-wide part, the
-  // partitions, the whole sort)
-  block_introsort<256>(key, L, Lp, Rp, bsl, VoxLess32{}, nullptr, c.dbg_phase >= 100 ? c.dbg_phase - 100 : 1 << 30);
-  if (c.dbg_phase <= 102) return;
-  uint16_t* cpos = Lp;  // the sort's scratch is free again
-  for (int t = tid; t < L; t += nt) cpos[t] = gc[t];
+  for (int t = tid; t < L; t += nt) {
+    key[t] = gk[t];
+    cpos[t] = gc[t];
+  }
+  __syncthreads();
   const float4* lp = d.loam + base + sp;
   float4* out = d.lflat_tmp + base + sp;
   const int wv = tid >> 6, ln = lane_id();

@@ -60,6 +60,9 @@ struct LLSR_HIDDEN llsr_handle {
   bool last_rec = false, s2s_rec = false, mo_rec = false;
   llsr::DevBufs d{};
   llsr_host::DevMem pool;
+  llsr_host::DevMem vox_mem;   // vox's items, then its counters
+  llsr::VoxRanges vox{};       // the PCL-order VoxelGrid's range list, sized for max_batch (llsr_device.h)
+  int vox_waves = 0;           // k_vox_leaf's largest grid (vox_leaf_waves)
   llsr_host::DevMem d_in;      // float4 [max_points]: single-scan staging
   llsr_host::DevMem d_vis;     // llsr_fetch_vis_clouds: 6 x HW points + 4 counts (on first use)
   llsr_host::DevMem d_off;     // int64 [2]

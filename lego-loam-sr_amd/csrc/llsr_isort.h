@@ -479,13 +479,15 @@ __device__ void exact_introsort(K* key, int n, uint16_t* Lp, uint16_t* Rp, int* 
 // chains of lopsided splits the voxel ids of a ring produce) are partitioned by the whole
 // workgroup, one at a time (block_partition: each thread classifies a contiguous chunk, one block
 // scan ranks the stops); every smaller range, or a large one whose depth limit is spent, goes to a
-// list that is dealt to the waves (largest first, each to the least loaded wave). Each wave then
-// finishes its ranges on its own as exact_introsort does: partition in LDS (stop lists at the
-// range's own offset of Lp / Rp), continue with the left part, the right part on the wave's private
-// stack; a range of at most 64 elements in registers (small_sort), one above 64 with no depth left
-// by wave_heap_sort. n <= 2048.
+// list (block_top_ranges). Each listed range is then finished by one wave as exact_introsort does
+// (wave_finish_range): partition in LDS (stop lists at the range's own offset of Lp / Rp), continue
+// with the left part, the right part on the wave's private stack; a range of at most 64 elements in
+// registers (seg_small_sort), one above 64 with no depth left by wave_heap_sort. block_introsort
+// deals the list to its four waves (largest first, each to the least loaded wave); the PCL-order
+// VoxelGrid (llsr_fa.hip) makes every listed range a work item of a one-wave kernel instead.
+// n <= 2048.
 constexpr int kBsBig = 512;
-constexpr int kBsList = 64;   // the dealt ranges: two per block partition at most, and few of those
+constexpr int kBsList = 64;   // the listed ranges of one array: at most kBsList - 1 (block_top_ranges)
 constexpr int kBsStack = 24;  // one entry per level of a path: <= depth limit (2 lg 2048 = 22) + 1
 struct BlockSortLds {
   int rng[kBsList];             // first | last << 12 | depth << 24
@@ -493,9 +495,14 @@ struct BlockSortLds {
   int big[kBsStack];            // the block's pending large ranges
   int stk[4][kBsStack];         // the waves' pending right parts
   int scan[16];
-  int nr, ks;
+  int ks;
   uint64_t piv;
 };
+// a range [first, last) with its remaining depth limit in one word
+__device__ __forceinline__ int bs_enc(int f, int e, int d) { return f | (e << 12) | (d << 24); }
+__device__ __forceinline__ int bs_first(int it) { return it & 0xfff; }
+__device__ __forceinline__ int bs_last(int it) { return (it >> 12) & 0xfff; }
+__device__ __forceinline__ int bs_depth(int it) { return (it >> 24) & 0x3f; }
 
 // One libstdc++ partition step of key[rf, rl) by one wave (rf + 1 < rl): the median of three to
 // rf, __unguarded_partition over (rf, rl) with the stop lists at Lp / Rp + rf; returns the cut.
@@ -633,77 +640,154 @@ __device__ __forceinline__ int block_partition(K* key, uint16_t* Lp, uint16_t* R
   return cut;
 }
 
-// prof (diagnostics only, k_debug_exact_sort): prof[0] = clocks of the block-wide part; per wave w,
-// prof[1 + 4 w + 0..3] = clocks in wave partitions, small_sort, wave_heap_sort, and idle at the end
+// The block-wide part: key[0, n), n > 64, partitioned by the whole workgroup (kNT threads) while a
+// range is above kBsBig and has depth left, left part first (the right part waits on the block's
+// stack); s.rng receives the resulting ranges, every element of [0, n) in exactly one. Returns
+// their number (uniform; every thread keeps a copy of the counters, thread 0 writes the arrays).
+// Near a full list the remaining ranges go to the list as they are, so a listed range above kBsBig
+// has either no depth left or came when the list was nearly full. The list never overflows: the
+// listed ranges, the pending large ones and the current one are at most kBsList - 2 before a step,
+// each step adds one, and nothing else does.
 template <int kNT, class K, class Lt>
-__device__ __forceinline__ void block_introsort(K* key, int n, uint16_t* Lp, uint16_t* Rp, BlockSortLds& s, Lt lt,
-                                                long long* prof = nullptr, int stop = 1 << 30) {
-  static_assert(kNT == 256, "block_introsort: four waves");
-  const int tid = threadIdx.x, l = lane_id(), w = tid >> 6;
-  long long tc = prof ? clock64() : 0, tpw = 0, tsm = 0, thp = 0;
-  auto stamp = [&](long long& acc) {
-    if (prof) {
+__device__ __forceinline__ int block_top_ranges(K* key, int n, uint16_t* Lp, uint16_t* Rp, BlockSortLds& s, Lt lt) {
+  const int tid = threadIdx.x;
+  int rf = 0, rl = n, rd = 2 * (31 - __clz(n));
+  int nbig = 0, nr = 0;
+  while (true) {
+    while (rl - rf > kBsBig && rd > 0 && nr + nbig < kBsList - 2) {
+      rd--;
+      const int cut = block_partition<kNT>(key, Lp, Rp, rf, rl, s, lt);
+      if (rl - cut > kBsBig && rd > 0) {
+        if (nbig >= kBsStack) __builtin_trap();  // cannot: <= one entry per level of the path
+        if (tid == 0) s.big[nbig] = bs_enc(cut, rl, rd);
+        ++nbig;
+      } else if (rl > cut) {
+        if (tid == 0) s.rng[nr] = bs_enc(cut, rl, rd);
+        ++nr;
+      }
+      rl = cut;
+    }
+    if (rl > rf) {
+      if (tid == 0) s.rng[nr] = bs_enc(rf, rl, rd);
+      ++nr;
+    }
+    if (nbig == 0) break;
+    __syncthreads();
+    --nbig;
+    const int it = s.big[nbig];
+    rf = bs_first(it);
+    rl = bs_last(it);
+    rd = bs_depth(it);
+  }
+  __syncthreads();
+  return nr;
+}
+
+// Consecutive ranges of at most 64 elements (left-first order emits them in position order) are
+// collected in a window of <= 64 lanes and finished together by seg_small_sort.
+struct SmallWindow {
+  int wf = 0, wn = 0, wdep = 0;  // wdep: the depth limit of the range that starts at this lane
+  unsigned long long wb = 0ull;
+  template <class K, class Lt>
+  __device__ __forceinline__ void flush(K* key, uint16_t* Lp, uint16_t* Rp, Lt lt) {
+    if (wn > 1) seg_small_sort(key, Lp, Rp, wf, wn, wb, wdep, lt);
+    wn = 0;
+  }
+  template <class K, class Lt>
+  __device__ __forceinline__ void emit(K* key, uint16_t* Lp, uint16_t* Rp, int rf, int rl, int rd, Lt lt) {
+    const int l = lane_id(), len = rl - rf;
+    if (len <= 0) return;
+    if (wn > 0 && rf == wf + wn && wn + len <= 64) {
+      wb |= 1ull << wn;
+      if (l == wn) wdep = rd;
+      wn += len;
+    } else {
+      flush(key, Lp, Rp, lt);
+      wf = rf;
+      wn = len;
+      wb = 1ull;
+      if (l == 0) wdep = rd;
+    }
+  }
+};
+// diagnostics only (k_debug_exact_sort): the clocks a wave spends in wave partitions, small sorts
+// and heap sorts
+struct SortClocks {
+  bool on = false;
+  long long tc = 0, tpw = 0, tsm = 0, thp = 0;
+  __device__ __forceinline__ void stamp(long long& acc) {
+    if (on) {
       const long long t1 = clock64();
       acc += t1 - tc;
       tc = t1;
     }
-  };
+  }
+};
+
+// One wave finishes key[rf, rl) with depth limit rd on its own: wave_partition while the range is
+// above 64 and has depth left, left part first with the right part on the wave's stack stk
+// (kBsStack ints); a range of at most 64 goes to the window (the caller flushes it after its last
+// range), one above 64 with no depth left to wave_heap_sort.
+template <class K, class Lt>
+__device__ __forceinline__ void wave_finish_range(K* key, uint16_t* Lp, uint16_t* Rp, int* stk, int rf, int rl, int rd,
+                                                  SmallWindow& win, SortClocks& ck, Lt lt) {
+  const int l = lane_id();
+  int sp = 0;
+  while (true) {
+    while (rl - rf > 64 && rd > 0) {
+      rd--;
+      const int cut = wave_partition(key, Lp, Rp, rf, rl, lt);
+      if (sp >= kBsStack) __builtin_trap();  // cannot: <= one entry per level of the path
+      if (l == 0) stk[sp] = bs_enc(cut, rl, rd);
+      ++sp;
+      rl = cut;
+    }
+    ck.stamp(ck.tpw);
+    if (rl - rf > 64) {
+      wave_heap_sort(key, rf, rl, lt);  // depth limit spent: __partial_sort
+      ck.stamp(ck.thp);
+    } else {
+      win.emit(key, Lp, Rp, rf, rl, rd, lt);
+      ck.stamp(ck.tsm);
+    }
+    wave_sync_lds();
+    if (sp == 0) break;
+    --sp;
+    const int nx = stk[sp];
+    rf = bs_first(nx);
+    rl = bs_last(nx);
+    rd = bs_depth(nx);
+  }
+}
+
+// prof (diagnostics only, k_debug_exact_sort): prof[0] = clocks of the block-wide part; per wave w,
+// prof[1 + 4 w + 0..3] = clocks in wave partitions, small_sort, wave_heap_sort, and idle at the end
+template <int kNT, class K, class Lt>
+__device__ __forceinline__ void block_introsort(K* key, int n, uint16_t* Lp, uint16_t* Rp, BlockSortLds& s, Lt lt,
+                                                long long* prof = nullptr) {
+  static_assert(kNT == 256, "block_introsort: four waves");
+  const int tid = threadIdx.x, l = lane_id(), w = tid >> 6;
+  SortClocks ck;
+  ck.on = prof != nullptr;
+  ck.tc = prof ? clock64() : 0;
   __syncthreads();  // key[0, n) written by the caller
   if (n <= 1) return;
-  const int lg = 31 - __clz(n);
   if (n <= 64) {  // std::sort's whole loop inside one small range
-    if (w == 0) small_sort(key, Lp, Rp, 0, n, 2 * lg, lt);
+    if (w == 0) small_sort(key, Lp, Rp, 0, n, 2 * (31 - __clz(n)), lt);
     __syncthreads();
     return;
   }
-  auto enc = [](int f, int e, int d) { return f | (e << 12) | (d << 24); };
-  // large ranges, block-wide, left part first (the right part waits on the block's stack); the
-  // counters are uniform copies every thread keeps (thread 0 writes the arrays). Near a full list
-  // the remaining ranges go to the list as they are (the waves finish any size).
-  {
-    int rf = 0, rl = n, rd = 2 * lg;
-    int nbig = 0, nr = 0;
-    while (true) {
-      while (rl - rf > kBsBig && rd > 0 && nr < kBsList - 2) {
-        rd--;
-        const int cut = block_partition<kNT>(key, Lp, Rp, rf, rl, s, lt);
-        if (rl - cut > kBsBig && rd > 0) {
-          if (nbig >= kBsStack) __builtin_trap();  // cannot: <= one entry per level of the path
-          if (tid == 0) s.big[nbig] = enc(cut, rl, rd);
-          ++nbig;
-        } else if (rl > cut) {
-          if (tid == 0) s.rng[nr] = enc(cut, rl, rd);
-          ++nr;
-        }
-        rl = cut;
-      }
-      if (rl > rf) {
-        if (tid == 0) s.rng[nr] = enc(rf, rl, rd);
-        ++nr;
-      }
-      if (nbig == 0) break;
-      __syncthreads();
-      --nbig;
-      const int it = s.big[nbig];
-      rf = it & 0xfff;
-      rl = (it >> 12) & 0xfff;
-      rd = (it >> 24) & 0x3f;
-    }
-    if (tid == 0) s.nr = nr;
-  }
-  __syncthreads();
-  if (prof && tid == 0) prof[0] = clock64() - tc;
-  if (stop <= 0) return;  // diagnostics (phase timing): the block-wide part only
+  const int nr = block_top_ranges<kNT>(key, n, Lp, Rp, s, lt);
+  if (prof && tid == 0) prof[0] = clock64() - ck.tc;
   // deal the list: largest first, each to the least loaded wave (elements as the load)
   if (w == 0) {
-    const int cnt = s.nr;
-    const int sz = l < cnt ? ((s.rng[l] >> 12) & 0xfff) - (s.rng[l] & 0xfff) : -1;
+    const int sz = l < nr ? bs_last(s.rng[l]) - bs_first(s.rng[l]) : -1;
     if (l == 0) {
       int ld0 = 0, ld1 = 0, ld2 = 0, ld3 = 0;
       unsigned long long taken = 0;
-      for (int r = 0; r < cnt; ++r) {
+      for (int r = 0; r < nr; ++r) {
         int best = 0, bs = -1;
-        for (int k = 0; k < cnt; ++k) {
+        for (int k = 0; k < nr; ++k) {
           const int z = __builtin_amdgcn_readlane(sz, k);
           if (!((taken >> k) & 1ull) && z > bs) { bs = z; best = k; }
         }
@@ -716,70 +800,20 @@ __device__ __forceinline__ void block_introsort(K* key, int n, uint16_t* Lp, uin
     }
   }
   __syncthreads();
-  // every wave finishes its ranges alone; consecutive ranges of at most 64 elements (left-first
-  // order emits them in position order) are collected in a window of <= 64 lanes and finished
-  // together by seg_small_sort
-  const int nr = s.nr;
-  int* stk = s.stk[w];
-  if (prof) tc = clock64();
-  int wf = 0, wn = 0, wdep = 0;
-  unsigned long long wb = 0ull;
-  auto flush = [&]() {
-    if (wn > 1 && stop > 1) seg_small_sort(key, Lp, Rp, wf, wn, wb, wdep, lt);  // stop 1: partitions only
-    wn = 0;
-  };
-  auto emit = [&](int rf, int rl, int rd) {
-    const int len = rl - rf;
-    if (len <= 0) return;
-    if (wn > 0 && rf == wf + wn && wn + len <= 64) {
-      wb |= 1ull << wn;
-      if (l == wn) wdep = rd;
-      wn += len;
-    } else {
-      flush();
-      wf = rf;
-      wn = len;
-      wb = 1ull;
-      if (l == 0) wdep = rd;
-    }
-  };
+  // every wave finishes its ranges alone
+  if (prof) ck.tc = clock64();
+  SmallWindow win;
   for (int k = 0; k < nr; ++k) {
     if (s.owner[k] != w) continue;
     const int it = s.rng[k];
-    int rf = it & 0xfff, rl = (it >> 12) & 0xfff, rd = (it >> 24) & 0x3f;
-    int sp = 0;
-    while (true) {
-      while (rl - rf > 64 && rd > 0) {
-        rd--;
-        const int cut = wave_partition(key, Lp, Rp, rf, rl, lt);
-        if (sp >= kBsStack) __builtin_trap();  // cannot: <= one entry per level of the path
-        if (l == 0) stk[sp] = enc(cut, rl, rd);
-        ++sp;
-        rl = cut;
-      }
-      stamp(tpw);
-      if (rl - rf > 64) {
-        wave_heap_sort(key, rf, rl, lt);  // depth limit spent: __partial_sort
-        stamp(thp);
-      } else {
-        emit(rf, rl, rd);
-        stamp(tsm);
-      }
-      wave_sync_lds();
-      if (sp == 0) break;
-      --sp;
-      const int nx = stk[sp];
-      rf = nx & 0xfff;
-      rl = (nx >> 12) & 0xfff;
-      rd = (nx >> 24) & 0x3f;
-    }
+    wave_finish_range(key, Lp, Rp, s.stk[w], bs_first(it), bs_last(it), bs_depth(it), win, ck, lt);
   }
-  flush();
-  stamp(tsm);
+  win.flush(key, Lp, Rp, lt);
+  ck.stamp(ck.tsm);
   long long tend = prof ? clock64() : 0;
   __syncthreads();
   if (prof && l == 0) {
-    prof[1 + 4 * w] = tpw; prof[2 + 4 * w] = tsm; prof[3 + 4 * w] = thp; prof[4 + 4 * w] = clock64() - tend;
+    prof[1 + 4 * w] = ck.tpw; prof[2 + 4 * w] = ck.tsm; prof[3 + 4 * w] = ck.thp; prof[4 + 4 * w] = clock64() - tend;
   }
 }
 
