@@ -29,7 +29,7 @@ __global__ void k_select_ring(DevCfg, DevBufs);
 __global__ void k_vox_top(DevCfg, DevBufs, VoxRanges);
 __global__ void k_vox_leaf(DevCfg, DevBufs, VoxRanges);
 __global__ void k_vox_sum(DevCfg, DevBufs);
-__global__ void k_debug_exact_sort(const float*, int, int*, long long*);
+__global__ void k_debug_exact_sort(const float*, int, int*);
 __global__ void k_debug_half_passed(const float*, int, uint8_t*);
 __global__ void k_fa_concat(DevCfg, DevBufs);
 __global__ void k_dbscan_adj(DevCfg, DevBufs, const float4* __restrict__);
@@ -447,9 +447,10 @@ extern "C" int32_t llsr_kernel_times_ms(llsr_handle* h, float* out, int32_t cap)
   return n;
 }
 
-// Diagnostics (not part of the ABI header): the device's exact libstdc++ std::sort (the per-ring
-// curvature sort's tie path and the PCL-order VoxelGrid, llsr_isort.h block_introsort) on n <= 2048 host values; out[k] = the
-// input position at sorted position k. For tests/test_gpu_features_ties.py.
+// Diagnostics (not part of the ABI header): the device's exact libstdc++ std::sort as k_select_ring
+// runs it on a ring's curvatures (llsr_isort.h block_introsort, one 256-thread workgroup) on
+// n <= 2048 host values; out[k] = the input position at sorted position k. For
+// tests/test_gpu_features_ties.py.
 extern "C" int32_t llsr_debug_exact_sort(const float* vals, int32_t n, int32_t* out) {
   if (!vals || !out || n < 0 || n > 2048) return LLSR_EINVAL;
   if (n == 0) return LLSR_OK;
@@ -457,7 +458,7 @@ extern "C" int32_t llsr_debug_exact_sort(const float* vals, int32_t n, int32_t* 
   if (llsr_host::alloc(dv, sizeof(float) * n) != hipSuccess || llsr_host::alloc(di, sizeof(int) * n) != hipSuccess)
     return LLSR_ENODEV;
   if (hipMemcpy(dv, vals, sizeof(float) * n, hipMemcpyHostToDevice) != hipSuccess) return LLSR_EIO;
-  k_debug_exact_sort<<<1, 256>>>((const float*)dv.get(), n, (int*)di.get(), nullptr);
+  k_debug_exact_sort<<<1, 256>>>((const float*)dv.get(), n, (int*)di.get());
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
       hipMemcpy(out, di, sizeof(int) * n, hipMemcpyDeviceToHost) != hipSuccess)
     return LLSR_EIO;
@@ -535,31 +536,13 @@ extern "C" float llsr_debug_exact_sort_ms(const float* vals, int32_t n, int32_t 
   if (llsr_host::alloc(dv, sizeof(float) * n) == hipSuccess && llsr_host::alloc(di, sizeof(int) * n) == hipSuccess &&
       llsr_host::create(e0) == hipSuccess && llsr_host::create(e1) == hipSuccess &&
       hipMemcpy(dv, vals, sizeof(float) * n, hipMemcpyHostToDevice) == hipSuccess) {
-    k_debug_exact_sort<<<1, 256>>>((const float*)dv.get(), n, (int*)di.get(), nullptr);
+    k_debug_exact_sort<<<1, 256>>>((const float*)dv.get(), n, (int*)di.get());
     (void)hipEventRecord(e0, nullptr);
-    for (int r = 0; r < reps; ++r) k_debug_exact_sort<<<1, 256>>>((const float*)dv.get(), n, (int*)di.get(), nullptr);
+    for (int r = 0; r < reps; ++r) k_debug_exact_sort<<<1, 256>>>((const float*)dv.get(), n, (int*)di.get());
     (void)hipEventRecord(e1, nullptr);
     if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ms /= reps;
   }
   return ms;
-}
-
-// Diagnostics (not part of the ABI header): one block_introsort of vals[0, n) with clock stamps:
-// cycles[0] = core clocks of the sort, cycles[1] = the block-wide part, cycles[2 + 4 w + 0..3] =
-// wave w's clocks in partitions, small sorts, heap sorts, and waiting at the end (18 values used).
-extern "C" int32_t llsr_debug_exact_sort_phases(const float* vals, int32_t n, long long* cycles) {
-  if (!vals || !cycles || n < 1 || n > 2048) return LLSR_EINVAL;
-  llsr_host::DevMem dv, di, dp;
-  if (llsr_host::alloc(dv, sizeof(float) * n) != hipSuccess || llsr_host::alloc(di, sizeof(int) * n) != hipSuccess ||
-      llsr_host::alloc(dp, 21 * sizeof(long long)) != hipSuccess || hipMemset(dp, 0, 21 * sizeof(long long)) != hipSuccess)
-    return LLSR_ENODEV;
-  if (hipMemcpy(dv, vals, sizeof(float) * n, hipMemcpyHostToDevice) != hipSuccess) return LLSR_EIO;
-  for (int r = 0; r < 3; ++r)  // warm: the last run counts
-    k_debug_exact_sort<<<1, 256>>>((const float*)dv.get(), n, (int*)di.get(), (long long*)dp.get());
-  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpy(cycles, dp, 21 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess)
-    return LLSR_EIO;
-  return LLSR_OK;
 }
 
 // After diagnostic launches of the selection stage that stop early: the whole stage once more with

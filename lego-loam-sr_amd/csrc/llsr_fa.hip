@@ -317,16 +317,13 @@ __device__ __forceinline__ int pow2_ceil(int n) {
 // Diagnostics (llsr_debug_exact_sort): the exact std::sort k_select_ring runs (block_introsort,
 // 256 threads) on one array of n <= kRingMax values; out receives the original positions in sorted
 // order.
-__global__ __launch_bounds__(256) void k_debug_exact_sort(const float* vals, int n, int* out, long long* prof) {
+__global__ __launch_bounds__(256) void k_debug_exact_sort(const float* vals, int n, int* out) {
   __shared__ uint64_t key[kRingMax];
   __shared__ uint16_t Lp[kRingMax], Rp[kRingMax];
   __shared__ BlockSortLds bsl;
   for (int t = threadIdx.x; t < n; t += 256) key[t] = ((uint64_t)__float_as_uint(vals[t]) << 32) | (uint32_t)t;
   __syncthreads();
-  long long t0 = 0;
-  if (prof && threadIdx.x == 0) t0 = clock64();
-  block_introsort<256>(key, n, Lp, Rp, bsl, CurvLess{}, prof ? prof + 1 : nullptr);
-  if (prof && threadIdx.x == 0) prof[0] = clock64() - t0;
+  block_introsort<256>(key, n, Lp, Rp, bsl, CurvLess{});
   for (int t = threadIdx.x; t < n; t += 256) out[t] = (int)(uint32_t)key[t];
 }
 
@@ -873,12 +870,11 @@ __global__ __launch_bounds__(256, 8) void k_vox_top(DevCfg c, DevBufs d, VoxRang
   // a leaf item: a wave of this workgroup finishes it here
   {
     SmallWindow win;
-    SortClocks ck;
     int nbig = 0;
     for (int k = 0; k < nr; ++k) {
       const int it = bsl.rng[k];
       if (bs_last(it) - bs_first(it) <= kBsBig || (nbig++ & 3) != w) continue;
-      wave_finish_range(key, Lp, Rp, bsl.stk[w], bs_first(it), bs_last(it), bs_depth(it), win, ck, lt);
+      wave_finish_range<kBsStack>(key, Lp, Rp, bsl.stk[w], bs_first(it), bs_last(it), bs_depth(it), win, lt);
     }
     win.flush(key, Lp, Rp, lt);
   }
@@ -918,8 +914,7 @@ __global__ __launch_bounds__(64, 8) void k_vox_leaf(DevCfg c, DevBufs d, VoxRang
     for (int t = l; t < n; t += 64) key[t] = gk[t];
     wave_sync_lds();
     SmallWindow win;
-    SortClocks ck;
-    wave_finish_range(key, Lp, Rp, stk, 0, n, bs_depth(it), win, ck, lt);
+    wave_finish_range<kBsStack>(key, Lp, Rp, stk, 0, n, bs_depth(it), win, lt);
     win.flush(key, Lp, Rp, lt);
     for (int t = l; t < n; t += 64) gk[t] = key[t];
     wave_sync_lds();

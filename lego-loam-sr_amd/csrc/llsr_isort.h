@@ -2,12 +2,35 @@
 // the reference sorts with a comparator that ignores part of the element, so the order of EQUAL
 // keys is whatever libstdc++'s introsort leaves and it changes results:
 //   * the per-ring cloudSmoothness sort by value (FA:1172): the greedy edge / flat pick visits tied
-//     candidates in that order (llsr_fa.hip);
+//     candidates in that order (llsr_fa.hip k_select_ring);
 //   * pcl::VoxelGrid's std::sort of (voxel id, point index) by voxel id (PCL 1.10 voxel_grid.hpp,
 //     every downSizeFilter of FA / MO): each centroid sums its voxel's points in that order
-//     (llsr_fa.hip's per-ring less-flat filter, llsr_map.hip's segmented filter).
+//     (llsr_fa.hip's per-ring less-flat filter k_vox_top / k_vox_leaf, llsr_map.hip's segmented
+//     filter k_is_level / k_is_leaf).
 // Keys are uint64 (sort key << 32 | payload) or uint32 (VoxLess32: dense voxel rank << 11 | candidate);
 // the comparator reads the sort-key bits only.
+//
+// What is reproduced: __introsort_loop (median of (first+1, mid, last-1) to first,
+// __unguarded_partition, depth limit 2*lg(n) -> heap sort), then __final_insertion_sort (threshold
+// 16). Each partition is evaluated in parallel: the k-th stop of the left scan over the original
+// range is L[k] (!(a < pivot)), of the right scan R[k] (!(pivot < a), from last-1 down to the pivot
+// slot); pairs k < k* = #{k : L[k] < R[k]} are swapped and the cut is R[k*-1] when k* > 0 and L[k*]
+// is missing or >= R[k*-1], else L[k*]. Sub-ranges are independent (the depth limit travels with
+// each), so the order in which they are processed does not change the result, and the final
+// insertion sort never crosses a leaf boundary, so it runs as one insertion sort per leaf.
+//
+// Each step is stated once, per executor:
+//   * a partition step: block_partition (a workgroup, ranges above kBsBig), wave_partition (one
+//     wave, ranges above 64), seg_small_sort (a segment of lanes, ranges of at most 64; it also
+//     finishes them); llsr_map.hip's k_is_level is the global-memory form for ranges above an LDS
+//     leaf. All pick the pivot with median3;
+//   * the heap sort of a range whose depth limit is spent: wave_heap_sort above 64 elements,
+//     reg_heap_sort inside seg_small_sort, heap_sort_range (one lane) in k_is_level;
+//   * one wave finishing a range on its own: wave_finish_range + SmallWindow. block_introsort
+//     (the curvature sort), k_vox_top, k_vox_leaf and k_is_leaf all run it.
+// The serial statement of this formulation is checked against std::sort by
+// tests/native/introsort_check.cpp; the device against the oracle's std::sort by
+// tests/test_gpu_features_ties.py, test_gpu_vox_split.py and test_gpu_map_sort.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,18 +39,6 @@
 
 namespace llsr {
 
-// The sort compares values only, so the order of EQUAL values is whatever libstdc++'s introsort
-// leaves, and it decides which of two tied candidates the greedy loop visits first. One wave
-// reproduces it on key[0, n) (value bits << 32 | ind): __introsort_loop (median of
-// (first+1, mid, last-1) to first, __unguarded_partition, depth limit 2*lg(n) -> heap sort),
-// then __final_insertion_sort (threshold 16). Each partition is evaluated in parallel: the k-th
-// stop of the left scan over the original range is L[k] (!(a < pivot)), of the right scan R[k]
-// (!(pivot < a), from last-1 down to the pivot slot); pairs k < k* = #{k : L[k] < R[k]} are
-// swapped and the cut is R[k*-1] when k* > 0 and L[k*] is missing or >= R[k*-1], else L[k*].
-// Sub-ranges are independent (the depth limit travels with each) and the final insertion sort
-// never crosses a leaf boundary, so it runs as one insertion sort per leaf. The serial statement
-// of this formulation is checked against std::sort by tests/native/introsort_check.cpp; the
-// device against the oracle's std::sort by tests/test_gpu_features_ties.py.
 __device__ __forceinline__ bool key_lt(uint64_t a, uint64_t b) {
   return __uint_as_float((uint32_t)(a >> 32)) < __uint_as_float((uint32_t)(b >> 32));
 }
@@ -63,6 +74,14 @@ struct PivotTest<uint32_t, VoxLess32> {
 __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
+}
+// __move_median_to_first(first, a, b, c): the index whose element libstdc++ swaps with `first`
+template <class K, class Lt>
+__device__ __forceinline__ int median3(K va, K vb, K vc, int a, int b, int c, Lt lt) {
+  int m;
+  if (lt(va, vb)) m = lt(vb, vc) ? b : (lt(va, vc) ? c : a);
+  else m = lt(va, vc) ? a : (lt(vb, vc) ? c : b);
+  return m;
 }
 // libstdc++ __adjust_heap (with __push_heap) on key[f, f+len), one lane
 template <class K, class Lt>
@@ -104,7 +123,6 @@ __device__ void heap_sort_range(K* key, int f, int l, Lt lt) {
     heap_adjust(key, f, 0, last - f, val, lt);
   }
 }
-constexpr int kSortStack = 64;
 
 // ---- ranges of at most 64 elements: the rest of their introsort in registers -----------------
 // Lane i holds element f + i. Partitions, the heap-sort fallback and the final insertion sort of
@@ -220,7 +238,8 @@ __device__ void seg_small_sort(K* key, uint16_t* Lp, uint16_t* Rp, int f, int n,
     const bool work = l < n && e - s > 16 && dd > 0;
     if (!ballot(work)) break;
     const unsigned long long segm = (e >= 64 ? ~0ull : ((1ull << e) - 1ull)) & ~((1ull << s) - 1ull);
-    // __move_median_to_first(first, first + 1, mid, last - 1) of this lane's segment
+    // __move_median_to_first(first, first + 1, mid, last - 1) of this lane's segment: median3's
+    // decision tree written out, because every leaf also selects the value (per lane, in registers)
     const int a = s + 1, b = s + (e - s) / 2, c = e - 1;
     const K va = shfl_k(v, a & 63), vb = shfl_k(v, b & 63), vc = shfl_k(v, c & 63), v0 = shfl_k(v, s);
     int mi;
@@ -309,11 +328,6 @@ __device__ void seg_small_sort(K* key, uint16_t* Lp, uint16_t* Rp, int f, int n,
   if (l < n) key[f + s0 + rank] = v;
   wave_sync_lds();
 }
-// one range key[f, f + n), n <= 64, with depth limit d
-template <class K, class Lt>
-__device__ __forceinline__ void small_sort(K* key, uint16_t* Lp, uint16_t* Rp, int f, int n, int d, Lt lt) {
-  seg_small_sort(key, Lp, Rp, f, n, 1ull, d, lt);
-}
 
 // ---- libstdc++'s heap sort of a range above 64 elements, by one wave ---------------------------
 // __make_heap: the sift-downs of one depth touch disjoint subtrees, so a depth's parents run on
@@ -392,103 +406,31 @@ __device__ void wave_heap_sort(K* key, int f, int e, Lt lt) {
   }
 }
 
-// Executed by one full wave (64 lanes). Lp / Rp: n uint16 each; stk: 3 * kStack ints.
-// key[0, n) ends up as std::sort leaves it. depth0 < 0: the whole array (depth limit 2 * lg(n));
-// else a sub-range of a larger sort that inherits the remaining depth limit of its parent range
-// (llsr_map.hip's segmented VoxelGrid, block_introsort's ranges). Ranges above 64 elements are
-// partitioned in LDS: one pass lists the L stops (ascending) and the R stops (ascending; R[k], the
-// k-th from the right, is Rp[nR - 1 - k]); each range of at most 64 is finished in registers
-// (small_sort), a range above 64 whose depth limit is spent by wave_heap_sort. The stack holds at
-// most one entry per level of the current path: <= depth limit + 1 entries.
-template <class K, class Lt, int kStack = kSortStack>
-__device__ void exact_introsort(K* key, int n, uint16_t* Lp, uint16_t* Rp, int* stk, Lt lt,
-                                int depth0 = -1) {
-  const int l = lane_id();
-  wave_sync_lds();
-  if (n <= 1) return;
-  const int lg = 31 - __clz(n);
-  int sp = 0;  // stack depth (wave-uniform)
-  int rf = 0, rl = n, rd = depth0 < 0 ? 2 * lg : depth0;
-  while (true) {
-    bool heaped = false;
-    while (rl - rf > 64) {
-      if (rd == 0) {
-        wave_heap_sort(key, rf, rl, lt);
-        heaped = true;
-        break;
-      }
-      rd--;
-      // __move_median_to_first(first, first+1, mid, last-1)
-      const int a = rf + 1, b = rf + (rl - rf) / 2, c = rl - 1;
-      const K va = key[a], vb = key[b], vc = key[c], vf = key[rf];
-      int m;
-      if (lt(va, vb)) m = lt(vb, vc) ? b : (lt(va, vc) ? c : a);
-      else m = lt(va, vc) ? a : (lt(vb, vc) ? c : b);
-      const K P = m == a ? va : (m == b ? vb : vc);
-      wave_sync_lds();
-      if (l == 0) { key[m] = vf; key[rf] = P; }
-      wave_sync_lds();
-      int nL = 0, nR = 0;
-      const PivotTest<K, Lt> pt(P, lt);
-      for (int c0 = rf; c0 < rl; c0 += 64) {
-        const int i = c0 + l;
-        const K v = i < rl ? key[i] : K(0);
-        const bool fl = i < rl && i > rf && !pt.below(v);
-        const bool fr = i < rl && !pt.above(v);
-        const unsigned long long in = lanes_below(rl - c0);
-        const unsigned long long mL = in & (c0 == rf ? ~1ull : ~0ull) & ~ballot(pt.below(v)), mR = in & ~ballot(pt.above(v));
-        if (fl) Lp[nL + lane_rank(mL)] = (uint16_t)i;
-        if (fr) Rp[nR + lane_rank(mR)] = (uint16_t)i;
-        nL += __popcll(mL);
-        nR += __popcll(mR);
-      }
-      wave_sync_lds();
-      const int nm = nL < nR ? nL : nR;
-      int ks = nm;  // first k with !(L[k] < R[k]) (monotone)
-      for (int c0 = 0; c0 < nm; c0 += 64) {
-        const int k = c0 + l;
-        const unsigned long long m = ballot(k < nm && !(Lp[k] < Rp[nR - 1 - k]));
-        if (m) { ks = c0 + __ffsll((long long)m) - 1; break; }
-      }
-      const int cut = (ks > 0 && (ks >= nL || Lp[ks] >= Rp[nR - ks])) ? Rp[nR - ks] : Lp[ks];
-      for (int k = l; k < ks; k += 64) {
-        const int a2 = Lp[k], b2 = Rp[nR - 1 - k];
-        const K t = key[a2]; key[a2] = key[b2]; key[b2] = t;
-      }
-      wave_sync_lds();
-      // the right part waits; the left part continues here (one entry per level of the path: at
-      // most the depth limit; a full stack traps instead of overrunning into its neighbours)
-      if (sp >= kStack) __builtin_trap();
-      if (l == 0) { stk[3 * sp] = cut; stk[3 * sp + 1] = rl; stk[3 * sp + 2] = rd; }
-      ++sp;
-      rl = cut;
-    }
-    if (!heaped && rl - rf > 1) small_sort(key, Lp, Rp, rf, rl - rf, rd, lt);
-    wave_sync_lds();
-    if (sp == 0) break;
-    --sp;
-    rf = stk[3 * sp]; rl = stk[3 * sp + 1]; rd = stk[3 * sp + 2];
-  }
-  wave_sync_lds();
-}
-
 // ---- the whole workgroup on one array ----------------------------------------------------------
-// block_introsort: the same std::sort by the workgroup. libstdc++'s recursion only ever touches
-// disjoint sub-ranges, each carrying its own depth limit, so the order in which they are processed
-// does not change the result. Ranges above kBsBig elements (the top of the recursion, and the long
-// chains of lopsided splits the voxel ids of a ring produce) are partitioned by the whole
-// workgroup, one at a time (block_partition: each thread classifies a contiguous chunk, one block
-// scan ranks the stops); every smaller range, or a large one whose depth limit is spent, goes to a
-// list (block_top_ranges). Each listed range is then finished by one wave as exact_introsort does
-// (wave_finish_range): partition in LDS (stop lists at the range's own offset of Lp / Rp), continue
-// with the left part, the right part on the wave's private stack; a range of at most 64 elements in
-// registers (seg_small_sort), one above 64 with no depth left by wave_heap_sort. block_introsort
-// deals the list to its four waves (largest first, each to the least loaded wave); the PCL-order
-// VoxelGrid (llsr_fa.hip) makes every listed range a work item of a one-wave kernel instead.
-// n <= 2048.
+// block_introsort: std::sort of key[0, n), n <= 2048, by the workgroup. Ranges above kBsBig
+// elements (the top of the recursion, and the long chains of lopsided splits the voxel ids of a
+// ring produce) are partitioned by the whole workgroup, one at a time (block_partition: each thread
+// classifies a contiguous chunk, one block scan ranks the stops); every smaller range, or a large
+// one whose depth limit is spent, goes to a list (block_top_ranges). Each listed range is then
+// finished by one wave (wave_finish_range): partition in LDS (wave_partition, stop lists at the
+// range's own offset of Lp / Rp), continue with the left part, the right part on the wave's private
+// stack; a range of at most 64 elements in registers (SmallWindow -> seg_small_sort), one above 64
+// with no depth left by wave_heap_sort. block_introsort deals the list to its four waves (largest
+// first, each to the least loaded wave); the PCL-order VoxelGrid (llsr_fa.hip) makes every listed
+// range a work item of a one-wave kernel instead, and llsr_map.hip's k_is_leaf gives a wave one
+// range of a cloud of any size.
+//
+// Stack capacity. A wave pushes one right part per partition step while it walks left and each
+// step takes one off the depth limit, so it holds at most as many entries as the depth limit its
+// range starts with. A range of an array of n <= 2048 starts with at most 2 lg 2048 = 22: kBsStack
+// = 24 (k_vox_top, k_vox_leaf, block_introsort, and the block's own stack of large ranges). A leaf
+// of k_is_leaf inherits what is left of 2 lg n of a cloud of any int count, up to 60: it passes 64,
+// which covers every depth limit bs_enc's 6 bits hold (<= 63). bs_enc's 12 bits hold positions up
+// to 4095: kRingMax = 2048 and llsr_map.hip's kIsLeaf = 1024 (static_assert there) fit. A full stack
+// traps instead of overrunning into its neighbours.
 constexpr int kBsBig = 512;
 constexpr int kBsList = 64;   // the listed ranges of one array: at most kBsList - 1 (block_top_ranges)
-constexpr int kBsStack = 24;  // one entry per level of a path: <= depth limit (2 lg 2048 = 22) + 1
+constexpr int kBsStack = 24;
 struct BlockSortLds {
   int rng[kBsList];             // first | last << 12 | depth << 24
   int owner[kBsList];           // the wave that finishes range k
@@ -512,9 +454,7 @@ __device__ __forceinline__ int wave_partition(K* key, uint16_t* Lp, uint16_t* Rp
   // __move_median_to_first(first, first+1, mid, last-1)
   const int a = rf + 1, b = rf + (rl - rf) / 2, c = rl - 1;
   const K va = key[a], vb = key[b], vc = key[c], vf = key[rf];
-  int m;
-  if (lt(va, vb)) m = lt(vb, vc) ? b : (lt(va, vc) ? c : a);
-  else m = lt(va, vc) ? a : (lt(vb, vc) ? c : b);
+  const int m = median3(va, vb, vc, a, b, c, lt);
   const K P = m == a ? va : (m == b ? vb : vc);
   wave_sync_lds();
   if (l == 0) { key[m] = vf; key[rf] = P; }
@@ -580,9 +520,7 @@ __device__ __forceinline__ int block_partition(K* key, uint16_t* Lp, uint16_t* R
   if (tid == 0) {  // __move_median_to_first(first, first+1, mid, last-1)
     const int a = rf + 1, b = rf + (rl - rf) / 2, c = rl - 1;
     const K va = key[a], vb = key[b], vc = key[c], vf = key[rf];
-    int m;
-    if (lt(va, vb)) m = lt(vb, vc) ? b : (lt(va, vc) ? c : a);
-    else m = lt(va, vc) ? a : (lt(vb, vc) ? c : b);
+    const int m = median3(va, vb, vc, a, b, c, lt);
     const K P = m == a ? va : (m == b ? vb : vc);
     key[m] = vf;
     key[rf] = P;
@@ -710,46 +648,26 @@ struct SmallWindow {
     }
   }
 };
-// diagnostics only (k_debug_exact_sort): the clocks a wave spends in wave partitions, small sorts
-// and heap sorts
-struct SortClocks {
-  bool on = false;
-  long long tc = 0, tpw = 0, tsm = 0, thp = 0;
-  __device__ __forceinline__ void stamp(long long& acc) {
-    if (on) {
-      const long long t1 = clock64();
-      acc += t1 - tc;
-      tc = t1;
-    }
-  }
-};
-
 // One wave finishes key[rf, rl) with depth limit rd on its own: wave_partition while the range is
-// above 64 and has depth left, left part first with the right part on the wave's stack stk
-// (kBsStack ints); a range of at most 64 goes to the window (the caller flushes it after its last
-// range), one above 64 with no depth left to wave_heap_sort.
-template <class K, class Lt>
+// above 64 and has depth left, left part first with the right part on the wave's stack stk (kStack
+// ints, at least rd: "Stack capacity" above); a range of at most 64 goes to the window (the caller
+// flushes it after its last range), one above 64 with no depth left to wave_heap_sort.
+template <int kStack, class K, class Lt>
 __device__ __forceinline__ void wave_finish_range(K* key, uint16_t* Lp, uint16_t* Rp, int* stk, int rf, int rl, int rd,
-                                                  SmallWindow& win, SortClocks& ck, Lt lt) {
+                                                  SmallWindow& win, Lt lt) {
   const int l = lane_id();
   int sp = 0;
   while (true) {
     while (rl - rf > 64 && rd > 0) {
       rd--;
       const int cut = wave_partition(key, Lp, Rp, rf, rl, lt);
-      if (sp >= kBsStack) __builtin_trap();  // cannot: <= one entry per level of the path
+      if (sp >= kStack) __builtin_trap();  // cannot: <= one entry per level of the path
       if (l == 0) stk[sp] = bs_enc(cut, rl, rd);
       ++sp;
       rl = cut;
     }
-    ck.stamp(ck.tpw);
-    if (rl - rf > 64) {
-      wave_heap_sort(key, rf, rl, lt);  // depth limit spent: __partial_sort
-      ck.stamp(ck.thp);
-    } else {
-      win.emit(key, Lp, Rp, rf, rl, rd, lt);
-      ck.stamp(ck.tsm);
-    }
+    if (rl - rf > 64) wave_heap_sort(key, rf, rl, lt);  // depth limit spent: __partial_sort
+    else win.emit(key, Lp, Rp, rf, rl, rd, lt);
     wave_sync_lds();
     if (sp == 0) break;
     --sp;
@@ -760,25 +678,18 @@ __device__ __forceinline__ void wave_finish_range(K* key, uint16_t* Lp, uint16_t
   }
 }
 
-// prof (diagnostics only, k_debug_exact_sort): prof[0] = clocks of the block-wide part; per wave w,
-// prof[1 + 4 w + 0..3] = clocks in wave partitions, small_sort, wave_heap_sort, and idle at the end
 template <int kNT, class K, class Lt>
-__device__ __forceinline__ void block_introsort(K* key, int n, uint16_t* Lp, uint16_t* Rp, BlockSortLds& s, Lt lt,
-                                                long long* prof = nullptr) {
+__device__ __forceinline__ void block_introsort(K* key, int n, uint16_t* Lp, uint16_t* Rp, BlockSortLds& s, Lt lt) {
   static_assert(kNT == 256, "block_introsort: four waves");
   const int tid = threadIdx.x, l = lane_id(), w = tid >> 6;
-  SortClocks ck;
-  ck.on = prof != nullptr;
-  ck.tc = prof ? clock64() : 0;
   __syncthreads();  // key[0, n) written by the caller
   if (n <= 1) return;
   if (n <= 64) {  // std::sort's whole loop inside one small range
-    if (w == 0) small_sort(key, Lp, Rp, 0, n, 2 * (31 - __clz(n)), lt);
+    if (w == 0) seg_small_sort(key, Lp, Rp, 0, n, 1ull, 2 * (31 - __clz(n)), lt);
     __syncthreads();
     return;
   }
   const int nr = block_top_ranges<kNT>(key, n, Lp, Rp, s, lt);
-  if (prof && tid == 0) prof[0] = clock64() - ck.tc;
   // deal the list: largest first, each to the least loaded wave (elements as the load)
   if (w == 0) {
     const int sz = l < nr ? bs_last(s.rng[l]) - bs_first(s.rng[l]) : -1;
@@ -801,20 +712,14 @@ __device__ __forceinline__ void block_introsort(K* key, int n, uint16_t* Lp, uin
   }
   __syncthreads();
   // every wave finishes its ranges alone
-  if (prof) ck.tc = clock64();
   SmallWindow win;
   for (int k = 0; k < nr; ++k) {
     if (s.owner[k] != w) continue;
     const int it = s.rng[k];
-    wave_finish_range(key, Lp, Rp, s.stk[w], bs_first(it), bs_last(it), bs_depth(it), win, ck, lt);
+    wave_finish_range<kBsStack>(key, Lp, Rp, s.stk[w], bs_first(it), bs_last(it), bs_depth(it), win, lt);
   }
   win.flush(key, Lp, Rp, lt);
-  ck.stamp(ck.tsm);
-  long long tend = prof ? clock64() : 0;
   __syncthreads();
-  if (prof && l == 0) {
-    prof[1 + 4 * w] = ck.tpw; prof[2 + 4 * w] = ck.tsm; prof[3 + 4 * w] = ck.thp; prof[4 + 4 * w] = clock64() - tend;
-  }
 }
 
 }  // namespace llsr

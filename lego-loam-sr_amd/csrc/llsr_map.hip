@@ -161,15 +161,17 @@ __global__ __launch_bounds__(256) void k_vg_keys(const Chunk* ch, const VgSeg* s
 // ---- std::sort(index_vector) by voxel id, exactly as libstdc++ leaves equal ids ----------------
 // Every segment is sorted on its own (llsr_isort.h): ranges above kIsLeaf are partitioned in
 // global memory, one 1024-thread workgroup per range and level (k_is_level: the same parallel
-// statement of __unguarded_partition as the wave version, with the stop lists in Lb / Rb); ranges
+// statement of __unguarded_partition as wave_partition, with the stop lists in Lb / Rb); ranges
 // of at most kIsLeaf elements finish in LDS, one wave each, with the depth limit they inherited
-// (k_is_leaf). A range whose depth limit runs out above kIsLeaf is heap-sorted by one lane (the
-// median-of-3 killer case; never met by point clouds).
+// (k_is_leaf: wave_finish_range + SmallWindow, as the per-ring filter's k_vox_leaf). A range whose
+// depth limit runs out above kIsLeaf is heap-sorted by one lane (the median-of-3 killer case; never
+// met by point clouds).
 struct IsRange {
   long long f, l;  // [f, l) in the packed key array
   int d, pad;      // remaining depth limit
 };
 constexpr int kIsLeaf = 1024;  // measured: 2048 -> 1024 local map 355 -> 369 extracts/s (512: same)
+static_assert(kIsLeaf < 4096, "a leaf's positions travel in bs_enc's 12 bits");
 constexpr int kIsT = 1024;       // threads of k_is_level
 constexpr int kIsE = 4;          // elements per lane per tile
 
@@ -198,9 +200,7 @@ __global__ __launch_bounds__(kIsT) void k_is_level(unsigned long long* kk, const
   }
   if (t == 0) {  // __move_median_to_first(first, first + 1, mid, last - 1)
     const int x = 1, y = n / 2, z = n - 1;
-    int m;
-    if (lt(a[x], a[y])) m = lt(a[y], a[z]) ? y : (lt(a[x], a[z]) ? z : x);
-    else m = lt(a[x], a[z]) ? x : (lt(a[y], a[z]) ? z : y);
+    const int m = median3(a[x], a[y], a[z], x, y, z, lt);
     const unsigned long long v = a[0]; a[0] = a[m]; a[m] = v;
   }
   __syncthreads();
@@ -281,16 +281,22 @@ __global__ __launch_bounds__(kIsT) void k_is_level(unsigned long long* kk, const
   }
 }
 
-// One wave per range of at most kIsLeaf elements: the rest of its introsort, in LDS.
+// One wave per range of at most kIsLeaf elements: the rest of its introsort, in LDS. The range
+// inherits what is left of its cloud's depth limit (2 lg n of an int count: up to 60), and the wave
+// can hold that many pending right parts: a stack of 64 (llsr_isort.h, "Stack capacity").
+constexpr int kIsStack = 64;
 __global__ __launch_bounds__(64) void k_is_leaf(unsigned long long* kk, const IsRange* leaves) {
   __shared__ uint64_t key[kIsLeaf];
   __shared__ uint16_t Lp[kIsLeaf], Rp[kIsLeaf];
-  __shared__ int stk[3 * kSortStack];
+  __shared__ int stk[kIsStack];
   const IsRange r = leaves[blockIdx.x];
   const int n = (int)(r.l - r.f);
+  const VoxLess lt{};
   for (int k = threadIdx.x; k < n; k += 64) key[k] = kk[r.f + k];
   wave_sync_lds();
-  exact_introsort(key, n, Lp, Rp, stk, VoxLess{}, r.d);
+  SmallWindow win;
+  wave_finish_range<kIsStack>(key, Lp, Rp, stk, 0, n, r.d, win, lt);
+  win.flush(key, Lp, Rp, lt);
   for (int k = threadIdx.x; k < n; k += 64) kk[r.f + k] = key[k];
 }
 

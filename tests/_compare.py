@@ -2,8 +2,8 @@
 
 Bar: bit-exact for every array — integer / index / label arrays and every float
 array, the VoxelGrid centroids of the less-flat cloud included: the device sums each voxel's points
-in the order libstdc++'s std::sort leaves PCL's index_vector (llsr_fa.hip, exact_introsort with the
-voxel-id comparator), as the oracle's PCL statement does.
+in the order libstdc++'s std::sort leaves PCL's index_vector (llsr_fa.hip k_vox_top / k_vox_leaf,
+llsr_isort.h's introsort with the voxel-rank comparator), as the oracle's PCL statement does.
 """
 import numpy as np
 

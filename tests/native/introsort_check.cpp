@@ -14,7 +14,7 @@
 //     with each range); the final insertion sort never moves an element across a leaf boundary,
 //     so it is one insertion sort per leaf block.
 // This program checks that formulation (written serially here, the same arithmetic as
-// llsr_fa.hip's exact_introsort) against std::sort on tie-heavy inputs, including inputs that
+// llsr_isort.h's partitions) against std::sort on tie-heavy inputs, including inputs that
 // exhaust the depth limit. Prints "<cases> <mismatches> <heap_fallbacks>"; exit 1 on mismatch.
 #include <algorithm>
 #include <cstdint>

@@ -2,7 +2,7 @@
 
 * Ties in the per-ring curvature sort (FA:1172, std::sort by value only): 4-fold symmetric scans
   repeat every curvature exactly, so libstdc++'s order of equal values decides the order of the
-  edge / flat lists; the device takes its exact introsort path (llsr_fa.hip exact_introsort) and
+  edge / flat lists; the device takes its exact introsort path (llsr_isort.h block_introsort) and
   must match the oracle's real std::sort bit for bit, over a sequence (carry-over state).
 * The phantom entry cloudSmoothness[4]: an exact zero curvature in ring 0 can take position 4 and
   its index is visited first by the next frame's flat loop (tests/test_introsort.py shows the

@@ -1,5 +1,5 @@
 """CPU: the wave-parallel statement of libstdc++'s std::sort that the device uses for the per-ring
-curvature sort's tie path (FA:1172; llsr_fa.hip exact_introsort) equals std::sort on 30k
+curvature sort's tie path (FA:1172; llsr_isort.h block_introsort) equals std::sort on 30k
 tie-heavy arrays, including median-of-3 killers that exhaust the depth limit (heap-sort fallback)
 — tests/native/introsort_check.cpp. The scenes that make ties decide the feature lists are checked
 here against the oracle; the device is compared with them in tests/test_gpu_features_ties.py."""
