@@ -39,12 +39,13 @@ const char* llsr_build_id(void);
 #define LLSR_EIO (-5)
 
 #define LLSR_LIDAR_VLP16 0
+#define LLSR_LIDAR_VLP32C 1
 #define LLSR_LIDAR_HDL64E 2
 
 #define LLSR_MODE_FAITHFUL 0
 #define LLSR_MODE_LM_APPLIED 1
 
-/* Mirrors the ROS2 parameters of the three nodes (loam_config.yaml:1-67 / 137-203;
+/* Mirrors the ROS2 parameters of the three nodes (loam_config.yaml:1-67 / 69-135 / 137-203;
  * read at imageProjection.cpp:80-121, featureAssociation.cpp:112-154). Angles in degrees,
  * exactly as in the YAML; the library applies the reference's conversions. */
 typedef struct llsr_config {
@@ -55,7 +56,7 @@ typedef struct llsr_config {
   float sensor_mount_angle;        /* deg (read but unused by groundRemovalOurs) */
   int32_t ground_scan_index;
   int32_t use_kitti;               /* ground angle D = 60/25 deg by row (IP:561-566) */
-  int32_t use_vlp32c;              /* must be 0: VLP-32c row-histogram branch is not built */
+  int32_t use_vlp32c;              /* rows by observed-elevation rank (IP:349-427), see below */
   float segment_theta;             /* deg */
   int32_t segment_valid_point_num;
   int32_t segment_valid_line_num;
@@ -73,7 +74,25 @@ typedef struct llsr_config {
   int32_t mode;                    /* LLSR_MODE_* */
 } llsr_config;
 
-/* Fill *cfg with the YAML block for `lidar` (LLSR_LIDAR_VLP16 / LLSR_LIDAR_HDL64E). */
+/* use_vlp32c (IP:349-427, 567-568). A point's row is not computed from its elevation: every
+ * finite point of the scan falls into the 0.335 deg elevation bin
+ *   temp = int((asinf(z / range) + ang_bottom) / (0.335 * DEG_TO_RAD)),
+ * before any column or range test, and the row of a point with temp >= 0 is the RANK of its bin
+ * among the distinct non-negative bins observed in this scan (vertical_raw2, llsr_row_bins). Points
+ * with temp < 0 are skipped; the column and range < 0.1 tests follow as in the plain branch. The
+ * ground column test takes D = 25 deg on every row unless use_kitti is set too, which is tested
+ * first (D = 60 / 25 deg by row). Two cases the reference leaves undefined are defined here:
+ *  1. Overflow. The reference has no row < num_vertical_scans test and writes out of bounds when a
+ *     scan shows more than H distinct bins. Here a point whose rank is >= H is dropped and claims
+ *     no cell; llsr_row_bins reports n_bins > H for that scan.
+ *  2. range == 0. z / range is NaN and its conversion to int is undefined; temp is defined as
+ *     negative (what x86-64's cvttsd2si gives): the point sets no bin and is skipped.
+ * The bin count is bounded by the configuration (344 for the shipped block); llsr_create returns
+ * LLSR_EINVAL when the bound exceeds 512. The reference's std::cout per point (IP:400) is not
+ * reproduced. */
+
+/* Fill *cfg with the YAML block for `lidar` (LLSR_LIDAR_VLP16 / LLSR_LIDAR_VLP32C /
+ * LLSR_LIDAR_HDL64E). */
 int32_t llsr_config_default(llsr_config* cfg, int32_t lidar);
 
 /* The less-flat VoxelGrid of the feature stage (surfPointsLessFlatScan, FA:1268-1270) averages
@@ -218,9 +237,17 @@ int32_t llsr_fetch_vis_clouds(llsr_handle* h, int32_t b, llsr_vis_out* out);
  * `out` must hold 8*B int32 (host). Synchronises. */
 int32_t llsr_batch_counts(llsr_handle* h, int32_t* out);
 
+/* use_vlp32c handles: slot b's vertical_raw2 of the last batch (IP:366-369), the ascending
+ * distinct elevation bins its finite points fell into. *n_bins receives their number (more than
+ * num_vertical_scans: the scan overflowed, see use_vlp32c above) and bins[0 .. min(cap, *n_bins))
+ * the bin numbers; bins may be NULL when cap is 0. LLSR_EINVAL on a handle without use_vlp32c.
+ * Synchronises. */
+int32_t llsr_row_bins(llsr_handle* h, int32_t b, int32_t* n_bins, int32_t* bins, int32_t cap);
+
 /* Per-kernel device time (ms per batch, averaged over every batch enqueued since profiling was
  * enabled) from HIP events recorded on each batch's launch stream between its kernels, in the
- * order of llsr_kernel_name(k). Synchronises. Returns the number of kernels written (<= cap). */
+ * order of llsr_kernel_name(k); k_row_bins, the last name, is written by use_vlp32c handles only.
+ * Synchronises. Returns the number of kernels written (<= cap). */
 int32_t llsr_kernel_times_ms(llsr_handle* h, float* out, int32_t cap);
 const char* llsr_kernel_name(int32_t k);
 /* Enable/disable per-kernel event timing; (re)enabling clears the accumulated averages. */
@@ -413,8 +440,8 @@ typedef struct llsr_map_config {
 } llsr_map_config;
 /* VLP-16 block: radius branch (enable_loop_closure 0), search num 50, the leaves above. */
 int32_t llsr_map_config_default(llsr_map_config* cfg);
-/* The block of loam_config.yaml for `lidar` (LLSR_LIDAR_VLP16: CFG:20-27; LLSR_LIDAR_HDL64E:
- * CFG:156-163, enable_loop_closure 1). */
+/* The block of loam_config.yaml for `lidar` (LLSR_LIDAR_VLP16: CFG:20-27; LLSR_LIDAR_VLP32C:
+ * CFG:88-95 and LLSR_LIDAR_HDL64E: CFG:156-163, both enable_loop_closure 1). */
 int32_t llsr_map_config_lidar(llsr_map_config* cfg, int32_t lidar);
 llsr_map* llsr_map_create(const llsr_map_config* cfg, int32_t hip_device);
 void llsr_map_destroy(llsr_map* m);

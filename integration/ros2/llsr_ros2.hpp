@@ -184,6 +184,10 @@ void append_xyzi(const float* xyzi, int32_t n, Cloud& c) {
   c.height = 1;
 }
 
+// `lidar` everywhere below is the launch file's lidar_type: VLP-16 -> LLSR_LIDAR_VLP16, VLP-32c ->
+// LLSR_LIDAR_VLP32C (use_vlp32c: rows by observed-elevation rank, ground D = 25 deg), HDL-64E ->
+// LLSR_LIDAR_HDL64E; llsr_config_default fills that block of loam_config.yaml.
+//
 // An llsr handle owned by one node thread (FA's scan-to-scan, MO's scan-to-map): one scan slot,
 // the LMs' buffers grow on first use. mode: LLSR_MODE_FAITHFUL / LLSR_MODE_LM_APPLIED (MO:1539-1545)
 class Handle {

@@ -17,7 +17,8 @@
 #include "llsr_libm.h"
 
 namespace llsr {
-__global__ void k_project(DevCfg, const float4*, const int64_t*, DevBufs);
+template <bool kRanked> __global__ void k_project(DevCfg, const float4*, const int64_t*, DevBufs, const uint32_t*);
+__global__ void k_row_bins(DevCfg, const float4*, const int64_t*, uint32_t*);
 __global__ void k_gather_column(DevCfg, const float4*, const int64_t*, DevBufs);
 __global__ void k_project_fused(DevCfg, const float4*, const int64_t*, DevBufs);
 __global__ void k_ground_add(DevCfg, DevBufs);
@@ -52,8 +53,17 @@ using namespace llsr;
 namespace {
 const char* kKernelNames[] = {"init",          "k_project",    "k_gather_column", "k_ground_add",
                               "k_ground_elev_ransac", "k_label", "k_segment",      "k_fa_points",
-                              "k_select_ring", "k_vox_pcl", "k_fa_concat", "k_dbscan_adj", "k_dbscan_merge"};
+                              "k_select_ring", "k_vox_pcl", "k_fa_concat", "k_dbscan_adj", "k_dbscan_merge",
+                              "k_row_bins"};
+static_assert(sizeof kKernelNames / sizeof *kKernelNames == kNumKernels, "one name per timed kernel");
 }  // namespace
+
+// use_vlp32c: one more than the largest elevation bin a point can fall into (IP:356 with asinf's
+// largest value, float pi / 2), in the reference's arithmetic; NaN-safe (a bad angle gives INT_MIN)
+static int row_bin_bound(const DevCfg& c) {
+  const int top = trunc_i32((double)(1.57079637050628662109375f + c.ip_angBottom) / (0.335 * (M_PI / 180.0)));
+  return top < 0 ? top : top + 1;
+}
 
 // The fused projection keeps the winning raw index per cell in LDS (k_project_fused).
 static int fused_lds(const DevCfg& c) { return c.HW * (int)sizeof(int); }
@@ -62,7 +72,8 @@ static int fused_lds(const DevCfg& c) { return c.HW * (int)sizeof(int); }
 static int label_lds(const DevCfg& c) { return c.HW * (int)(sizeof(int) + 1); }
 
 static int label_band_lds(const DevCfg& c) { return c.lbl_band * c.W * (int)sizeof(int); }
-static bool use_fused(const llsr_handle* h) { return h->dc.ccl_lds != 0; }
+// (a use_vlp32c handle ranks its rows first: always k_row_bins -> k_project<true> -> k_gather_column)
+static bool use_fused(const llsr_handle* h) { return h->dc.ccl_lds != 0 && !h->dc.use_vlp32c; }
 
 // k_segment / k_ground_elev_ransac (any multiple of 64 up to 1024 threads): 512 for range images
 // that fit LDS (VLP-16: three / two scans per CU instead of one; r06_v40, 0.289 -> 0.282 and
@@ -104,6 +115,12 @@ extern "C" int32_t llsr_config_default(llsr_config* c, int32_t lidar) {
     c->ground_scan_index = 7; c->use_kitti = 0;
     c->DBFr = 5.0f; c->RatioXY = 0.5f; c->RatioZ = 2.5f;
     c->edge_threshold = 0.03f; c->surf_threshold = 0.03f; c->nearest_feature_search_distance = 5.0f;
+  } else if (lidar == LLSR_LIDAR_VLP32C) {  // loam_config.yaml:69-135
+    c->num_vertical_scans = 32; c->num_horizontal_scans = 1800;
+    c->vertical_angle_bottom = -25.0f; c->vertical_angle_top = 15.0f;
+    c->ground_scan_index = 7; c->use_kitti = 0;
+    c->DBFr = 5.0f; c->RatioXY = 0.5f; c->RatioZ = 2.5f;
+    c->edge_threshold = 0.005f; c->surf_threshold = 0.005f; c->nearest_feature_search_distance = 5.0f;
   } else if (lidar == LLSR_LIDAR_HDL64E) {  // loam_config.yaml:137-203
     c->num_vertical_scans = 64; c->num_horizontal_scans = 1800;
     c->vertical_angle_bottom = -24.8f; c->vertical_angle_top = 2.0f;
@@ -114,11 +131,12 @@ extern "C" int32_t llsr_config_default(llsr_config* c, int32_t lidar) {
     return LLSR_EINVAL;
   }
   c->sensor_mount_angle = 0.0f;
-  c->use_vlp32c = 0;
+  c->use_vlp32c = lidar == LLSR_LIDAR_VLP32C ? 1 : 0;
   c->segment_theta = 60.0f; c->segment_valid_point_num = 5; c->segment_valid_line_num = 3;
   c->scan_period = 0.1f;
   c->mapping_frequency_divider = 1;
-  c->iterCountThres = 200; c->step_size = 1.0f; c->stop_thres = 0.05f;
+  c->iterCountThres = lidar == LLSR_LIDAR_VLP32C ? 50 : 200;  // CFG:98
+  c->step_size = 1.0f; c->stop_thres = 0.05f;
   c->mode = LLSR_MODE_FAITHFUL;
   return LLSR_OK;
 }
@@ -152,6 +170,7 @@ static void make_devcfg(const llsr_config& c, DevCfg& d) {
   d.gnd_cos[0] = llsr_libm::ground_cos_threshold(12.5f);
   d.gnd_cos[1] = llsr_libm::ground_cos_threshold(60.0f);
   d.gnd_cos[2] = llsr_libm::ground_cos_threshold(25.0f);
+  d.use_vlp32c = c.use_vlp32c ? 1 : 0;
   d.ccl_lds = (d.H <= 16 && d.HW <= 32000) ? 1 : 0;
   // 72 KB bands: two labelling workgroups per CU (a 512-scan HDL-64E batch runs in one round)
   // (at most 16 rows: a band root's LDS word keeps its members' rows in 16 bits)
@@ -176,7 +195,6 @@ extern "C" int32_t llsr_create(const llsr_config* cfg, int32_t hip_device, int32
                                int32_t max_points, llsr_handle** out) {
   if (!cfg || !out || max_batch < 1 || max_points < 1) return LLSR_EINVAL;
   *out = nullptr;
-  if (cfg->use_vlp32c) return LLSR_ENOSYS;
   if (cfg->num_vertical_scans < 2 || cfg->num_vertical_scans > 64 || cfg->num_horizontal_scans < 16 ||
       cfg->num_horizontal_scans > 2048)
     return LLSR_EINVAL;
@@ -191,7 +209,10 @@ extern "C" int32_t llsr_create(const llsr_config* cfg, int32_t hip_device, int32
   h->max_points = max_points;
   make_devcfg(*cfg, h->dc);
   const DevCfg& c = h->dc;
+  if (c.use_vlp32c && (row_bin_bound(c) < 1 || row_bin_bound(c) > kBinWords * 32)) return LLSR_EINVAL;
   if (hipSetDevice(hip_device) != hipSuccess) return LLSR_ENODEV;
+  if (c.use_vlp32c && llsr_host::alloc(h->row_bm, sizeof(uint32_t) * kBinWords * (size_t)max_batch) != hipSuccess)
+    return LLSR_ENOMEM;
   if (llsr_host::alloc_pool(h->pool, 4096, [&](llsr_host::Carver& cv) {
         llsr_host::feature_layout(cv, h->d, max_batch, c.H, c.HW, kCnt, kAdjCap * kAdjWords);
       }) != hipSuccess)
@@ -333,10 +354,15 @@ extern "C" int32_t llsr_reset_state(llsr_handle* h) {
 // Retire the oldest profiled batch: wait for its last event and add its kernel intervals.
 static void retire_oldest(llsr_handle* h) {
   const int slot = (h->ring_head - h->ring_used + llsr_handle::kRing) % llsr_handle::kRing;
-  (void)hipEventSynchronize(h->ev[slot][kNumKernels]);
-  for (int k = 0; k < kNumKernels; ++k) {
+  (void)hipEventSynchronize(h->ev[slot][kSeqKernels]);
+  for (int k = 0; k < kSeqKernels; ++k) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, h->ev[slot][k], h->ev[slot][k + 1]) == hipSuccess) h->ksum[k] += ms;
+  }
+  if (h->dc.use_vlp32c) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev[slot][kSeqKernels + 1], h->ev[slot][kSeqKernels + 2]) == hipSuccess)
+      h->ksum[kRowBins] += ms;
   }
   h->kbatches += 1;
   h->ring_used -= 1;
@@ -375,6 +401,15 @@ extern "C" int32_t llsr_process_batch(llsr_handle* h, const float* d_xyzi, const
     }
     ++k;
   };
+  // grid-stride kernels: ~16k workgroups in all, at least 4 per scan
+  const int gx = std::max(1, std::min((h->max_points + 255) / 256, std::max(4, 16384 / B)));
+  uint32_t* row_bm = static_cast<uint32_t*>(h->row_bm.get());
+  if (c.use_vlp32c) {  // the slots' observed elevation bins, ahead of the kernels every handle runs
+    HIP_OK(h, hipMemsetAsync(row_bm, 0, sizeof(uint32_t) * kBinWords * (size_t)B, s));
+    if (h->profiling) (void)hipEventRecord(evs[kSeqKernels + 1], s);
+    k_row_bins<<<dim3(gx, B), 256, 0, s>>>(c, pts, d_offsets, row_bm);
+    if (h->profiling) (void)hipEventRecord(evs[kSeqKernels + 2], s);
+  }
   mark();
   const bool fused = use_fused(h);
   if (!fused) HIP_OK(h, hipMemsetAsync(h->d.ccl_a, 0xFF, sizeof(int) * (size_t)B * c.HW, s));
@@ -385,9 +420,8 @@ extern "C" int32_t llsr_process_batch(llsr_handle* h, const float* d_xyzi, const
     mark();
     mark();
   } else {
-    // grid-stride kernels: ~16k workgroups in all, at least 4 per scan
-    const int gx = std::max(1, std::min((h->max_points + 255) / 256, std::max(4, 16384 / B)));
-    k_project<<<dim3(gx, B), 256, 0, s>>>(c, pts, d_offsets, h->d);
+    if (c.use_vlp32c) k_project<true><<<dim3(gx, B), 256, 0, s>>>(c, pts, d_offsets, h->d, row_bm);
+    else k_project<false><<<dim3(gx, B), 256, 0, s>>>(c, pts, d_offsets, h->d, nullptr);
     mark();
     k_gather_column<<<dim3((c.W + 63) / 64, B), 64, sizeof(int) * 64 * (c.H + 1), s>>>(c, pts, d_offsets, h->d);
     mark();
@@ -443,8 +477,28 @@ extern "C" int32_t llsr_kernel_times_ms(llsr_handle* h, float* out, int32_t cap)
   while (h->ring_used > 0) retire_oldest(h);
   if (h->kbatches == 0) return 0;
   int n = 0;
-  for (int k = 0; k < kNumKernels && n < cap; ++k, ++n) out[n] = (float)(h->ksum[k] / (double)h->kbatches);
+  // k_row_bins, the table's last entry, only where it runs
+  const int nk = h->dc.use_vlp32c ? kNumKernels : kSeqKernels;
+  for (int k = 0; k < nk && n < cap; ++k, ++n) out[n] = (float)(h->ksum[k] / (double)h->kbatches);
   return n;
+}
+
+extern "C" int32_t llsr_row_bins(llsr_handle* h, int32_t b, int32_t* n_bins, int32_t* bins, int32_t cap) {
+  if (!h || !n_bins || cap < 0 || (cap > 0 && !bins)) return LLSR_EINVAL;
+  if (!h->dc.use_vlp32c) return fail(h, LLSR_EINVAL, "llsr_row_bins needs a use_vlp32c handle");
+  if (b < 0 || b >= h->last_B) return fail(h, LLSR_ERANGE, "slot outside last batch");
+  int32_t rc = sync_last(h);
+  if (rc) return rc;
+  uint32_t bm[kBinWords];
+  HIP_OK(h, d2h(bm, static_cast<const uint32_t*>(h->row_bm.get()) + (size_t)b * kBinWords, kBinWords));
+  int n = 0;
+  for (int bin = 0; bin < kBinWords * 32; ++bin) {
+    if (!((bm[bin >> 5] >> (bin & 31)) & 1u)) continue;
+    if (n < cap) bins[n] = bin;
+    ++n;
+  }
+  *n_bins = n;
+  return LLSR_OK;
 }
 
 // Diagnostics (not part of the ABI header): the device's exact libstdc++ std::sort as k_select_ring

@@ -78,7 +78,9 @@ extern "C" int32_t llsr_mapping_init(llsr_handle* h, int32_t mo_mode, const llsr
   // both handle modes: llsr_mapping_batch refuses the faithful one itself, llsr_mapping_batch_odom runs it
   llsr_map_config mcfg;
   if (map_cfg) mcfg = *map_cfg;  // NULL: the YAML block of the handle's lidar
-  else llsr_map_config_lidar(&mcfg, h->dc.H == 64 ? LLSR_LIDAR_HDL64E : LLSR_LIDAR_VLP16);
+  else  // a use_vlp32c handle gets its own block whatever its H
+    llsr_map_config_lidar(&mcfg, h->cfg.use_vlp32c ? LLSR_LIDAR_VLP32C
+                                 : h->dc.H == 64   ? LLSR_LIDAR_HDL64E : LLSR_LIDAR_VLP16);
   if (mcfg.enable_loop_closure && mcfg.surrounding_keyframe_search_num < 1)
     return fail(h, LLSR_EINVAL, "surrounding_keyframe_search_num must be >= 1 with loop closure");
   HIP_OK(h, hipSetDevice(h->device));

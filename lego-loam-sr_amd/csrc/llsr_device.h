@@ -42,7 +42,13 @@ struct DevCfg {
   int lbl_band; // otherwise: rows per LDS union-find band of k_label<false> (band * W ints <= 72 KB: two workgroups per CU)
   int exact_vg;   // LLSR_VOXEL_ORDER_PCL: the less-flat VoxelGrid sums in std::sort's tie order
   int dbg_phase;  // diagnostics only: kernels return at phase boundary >= dbg_phase (default: never)
+  int use_vlp32c; // rows by observed-elevation rank (k_row_bins, k_project<true>); ground D = 25 deg unless use_kitti
 };
+
+// use_vlp32c: a slot's observed 0.335 deg elevation bins (IP:352-369) as a bitmap of kBinWords
+// words. Bin numbers stay below trunc((asinf(1) + ang_bottom) / 0.335 deg) + 1 (344 for the
+// shipped block); llsr_create refuses a configuration whose bound exceeds the bitmap.
+constexpr int kBinWords = 16;
 
 // Device buffers owned by the handle; every per-slot array has stride HW (or H for rings).
 struct DevBufs {

@@ -15,7 +15,11 @@
 
 #define LLSR_HIDDEN __attribute__((visibility("hidden")))
 
-constexpr int kNumKernels = 13;  // feature-batch kernels timed by the profiling ring
+constexpr int kSeqKernels = 13;  // feature-batch kernels every handle runs back to back
+// ... and, at the table's end, k_row_bins: a use_vlp32c handle runs it ahead of them, between two
+// events of its own
+constexpr int kNumKernels = kSeqKernels + 1;
+constexpr int kRowBins = kSeqKernels;
 
 // Pinned flag words and timing events of an LM stage (scan-to-map, scan-to-scan), made once.
 struct LLSR_HIDDEN LmAux {
@@ -66,6 +70,7 @@ struct LLSR_HIDDEN llsr_handle {
   llsr_host::DevMem d_in;      // float4 [max_points]: single-scan staging
   llsr_host::DevMem d_vis;     // llsr_fetch_vis_clouds: 6 x HW points + 4 counts (on first use)
   llsr_host::DevMem d_off;     // int64 [2]
+  llsr_host::DevMem row_bm;    // use_vlp32c: uint32 [max_batch][kBinWords] observed elevation bins
   int last_B = 0;
   const float4* last_pts = nullptr;  // inputs of the last batch (diagnostic re-launches only)
   const int64_t* last_off = nullptr;
@@ -73,7 +78,7 @@ struct LLSR_HIDDEN llsr_handle {
   bool debug_sync = false;  // LLSR_DEBUG_SYNC=1: wait after every feature-batch kernel, name a failing one
   // Event sets for up to kRing in-flight profiled batches; retired sets are summed into ksum.
   static constexpr int kRing = 64;
-  llsr_host::Event ev[kRing][kNumKernels + 1];
+  llsr_host::Event ev[kRing][kSeqKernels + 3];  // kSeqKernels + 1 boundaries, then k_row_bins' pair
   int ring_head = 0, ring_used = 0;
   double ksum[kNumKernels] = {};
   long long kbatches = 0;

@@ -115,6 +115,25 @@ __device__ __forceinline__ int project_cell_any(const DevCfg& c, float4 p, float
   return row;
 }
 
+// The VLP-32c branch's elevation bin (IP:354-356, 390-393): temp = int((va + _ang_bottom) /
+// (0.335 * DEG_TO_RAD)), a float sum over a double constant, truncated. range == 0 makes z / range
+// NaN, which trunc_i32 turns negative like the reference's cvttsd2si: no bin (include/llsr.h).
+__device__ __forceinline__ int row_bin(const DevCfg& c, float4 p, float* range_out) {
+  const float range = sqrt_(p.x * p.x + p.y * p.y + p.z * p.z);
+  *range_out = range;
+  const float va = asinf_(p.z / range);
+  return trunc_i32((double)(va + c.ip_angBottom) / (0.335 * (kPi / 180.0)));
+}
+
+// project_cell's column and range tests alone (IP:404-414): the column, or -1
+__device__ __forceinline__ int project_col(const DevCfg& c, float4 p, float range) {
+  const float ha = atan2f_(p.x, p.y);
+  int col = trunc_i32(-round(((double)ha - kPi / 2) / (double)c.ip_resX) + c.W * 0.5);
+  if (col >= c.W) col -= c.W;
+  if (col < 0 || col >= c.W || (double)range < 0.1) return -1;
+  return col;
+}
+
 // ---------------------------------------------------------------------------------------------
 // K1 project: removeNaNFromPointCloud (IP:198) + projectPointCloud row/col (IP:305-336).
 // One thread per raw point; the serial "last writer wins" of IP:337-347 becomes atomicMax of
@@ -127,10 +146,29 @@ __device__ __forceinline__ int project_cell_any(const DevCfg& c, float4 p, float
 // plain-store pass plus an atomicMax fix-up pass for colliding cells was slower, 0.61 ms.)
 // grid (ceil(maxN/256), B), block 256.
 // ---------------------------------------------------------------------------------------------
+// kRanked (use_vlp32c, IP:388-427): the row is the rank of the point's elevation bin among the
+// slot's observed bins (row_bm, built by k_row_bins): the workgroup keeps the bitmap and the
+// popcounts below each word in LDS, a point's row is the number of set bits below its bin. The
+// reference's order of tests: temp < 0, the column, range < 0.1; a rank >= H claims no cell
+// (include/llsr.h: the reference writes out of bounds there). The bin is recomputed, not kept.
+template <bool kRanked>
 __global__ __launch_bounds__(256) void k_project(DevCfg c, const float4* __restrict__ pts,
-                                                 const int64_t* __restrict__ off, DevBufs d) {
+                                                 const int64_t* __restrict__ off, DevBufs d,
+                                                 const uint32_t* __restrict__ row_bm) {
   const int b = blockIdx.y;
   const int64_t o0 = off[b], n = off[b + 1] - o0;
+  __shared__ uint32_t bm[kBinWords];
+  __shared__ int below[kBinWords];
+  if constexpr (kRanked) {
+    if (threadIdx.x < kBinWords) bm[threadIdx.x] = row_bm[(size_t)b * kBinWords + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x < kBinWords) {
+      int acc = 0;
+      for (int w = 0; w < (int)threadIdx.x; ++w) acc += __popc(bm[w]);
+      below[threadIdx.x] = acc;
+    }
+    __syncthreads();
+  }
   // grid-stride over the scan: every raw point is projected whatever the grid's width; the
   // finite-point count and first / last finite index are reduced per workgroup (3 atomics each)
   int npts = 0, first = INT_MAX, last = -1;
@@ -140,8 +178,17 @@ __global__ __launch_bounds__(256) void k_project(DevCfg c, const float4* __restr
     ++npts;
     first = min(first, (int)i);
     last = max(last, (int)i);
-    int col;
-    const int row = project_cell_any(c, p, 1.0f / c.ip_resY, 1.0f / c.ip_resX, &col);
+    int col, row;
+    if constexpr (kRanked) {
+      float range;
+      const int bin = row_bin(c, p, &range);
+      if (bin < 0 || bin >= kBinWords * 32) continue;
+      col = project_col(c, p, range);
+      row = below[bin >> 5] + __popc(bm[bin >> 5] & ((1u << (bin & 31)) - 1u));
+      if (col < 0 || row >= c.H) continue;
+    } else {
+      row = project_cell_any(c, p, 1.0f / c.ip_resY, 1.0f / c.ip_resX, &col);
+    }
     if (row >= 0) atomicMax(&d.ccl_a[(size_t)b * c.HW + (size_t)col * c.H + row], (int)i);
   }
   __shared__ int red[3][4];
@@ -164,6 +211,34 @@ __global__ __launch_bounds__(256) void k_project(DevCfg c, const float4* __restr
       atomicMax(&cnt[C_LAST], last);
     }
   }
+}
+template __global__ void k_project<false>(DevCfg, const float4*, const int64_t*, DevBufs, const uint32_t*);
+template __global__ void k_project<true>(DevCfg, const float4*, const int64_t*, DevBufs, const uint32_t*);
+
+// ---------------------------------------------------------------------------------------------
+// K0 row bins (use_vlp32c only): the first loop of the VLP-32c branch (IP:352-365) and the sorted
+// distinct bins vertical_raw2 (IP:366-369) as a bitmap per slot, bit `temp` set when a finite point
+// fell into elevation bin temp >= 0. It runs before any column or range test, as the reference
+// does. Each workgroup ORs its points' bins into an LDS bitmap and merges the non-zero words into
+// the slot's (cleared per batch on the batch's stream) with one atomic each.
+// grid (gx, B), block 256: the grid-stride shape of k_project.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_row_bins(DevCfg c, const float4* __restrict__ pts,
+                                                  const int64_t* __restrict__ off, uint32_t* __restrict__ row_bm) {
+  __shared__ uint32_t bm[kBinWords];
+  const int b = blockIdx.y;
+  const int64_t o0 = off[b], n = off[b + 1] - o0;
+  if (threadIdx.x < kBinWords) bm[threadIdx.x] = 0u;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 p = pts[o0 + i];
+    if (!finite3(p)) continue;
+    float range;
+    const int bin = row_bin(c, p, &range);
+    if (bin >= 0 && bin < kBinWords * 32) atomicOr(&bm[bin >> 5], 1u << (bin & 31));
+  }
+  __syncthreads();
+  if (threadIdx.x < kBinWords && bm[threadIdx.x]) atomicOr(&row_bm[(size_t)b * kBinWords + threadIdx.x], bm[threadIdx.x]);
 }
 
 // groundRemovalOurs' per-column test (IP:524-629) as a step over one column's state, so a lane can
@@ -189,7 +264,8 @@ __device__ __forceinline__ int8_t ground_step(const DevCfg& c, GndState& st, flo
     const float x = (TVx * st.RVx + TVy * st.RVy + TVz * st.RVz) /
                     (sqrt_(TVx * TVx + TVy * TVy + TVz * TVz) *
                      sqrt_(st.RVx * st.RVx + st.RVy * st.RVy + st.RVz * st.RVz));
-    const float xs = c.use_kitti ? (i < 16 ? c.gnd_cos[1] : c.gnd_cos[2]) : c.gnd_cos[0];
+    // IP:561-571: use_kitti is tested first, then use_vlp32c (25 deg on every row)
+    const float xs = c.use_kitti ? (i < 16 ? c.gnd_cos[1] : c.gnd_cos[2]) : c.use_vlp32c ? c.gnd_cos[2] : c.gnd_cos[0];
     if (x >= xs && x <= 1.0f) { st.RVx += TVx; st.RVy += TVy; st.RVz += TVz; g = 1; }
     else g = 0;
     st.lx = f.x; st.ly = f.y; st.lz = f.z;

@@ -666,9 +666,9 @@ extern "C" int32_t llsr_map_config_default(llsr_map_config* c) {
 
 extern "C" int32_t llsr_map_config_lidar(llsr_map_config* c, int32_t lidar) {
   if (!c) return LLSR_EINVAL;
-  if (lidar != LLSR_LIDAR_VLP16 && lidar != LLSR_LIDAR_HDL64E) return LLSR_EINVAL;
-  llsr_map_config_default(c);  // radius 50 and search num 50 in both blocks (CFG:26-27, 162-163)
-  c->enable_loop_closure = lidar == LLSR_LIDAR_HDL64E ? 1 : 0;  // CFG:159
+  if (lidar != LLSR_LIDAR_VLP16 && lidar != LLSR_LIDAR_VLP32C && lidar != LLSR_LIDAR_HDL64E) return LLSR_EINVAL;
+  llsr_map_config_default(c);  // radius 50 and search num 50 in every block (CFG:26-27, 94-95, 162-163)
+  c->enable_loop_closure = lidar == LLSR_LIDAR_VLP16 ? 0 : 1;  // CFG:23, 91, 159
   return LLSR_OK;
 }
 

@@ -47,7 +47,7 @@ EXPORTS = [
     "llsr_integrate_transformation", "llsr_transform_to_end", "llsr_odom_init", "llsr_odom_callback",
     "llsr_update_initial_guess", "llsr_odometry_batch_odom", "llsr_odometry_fetch_lm", "llsr_mapping_batch_odom",
     "llsr_global_map_config_default", "llsr_map_global", "llsr_map_save", "llsr_keypose_radius_sorted",
-    "llsr_mapping_global_map", "llsr_mapping_save_map",
+    "llsr_mapping_global_map", "llsr_mapping_save_map", "llsr_row_bins",
 ]
 
 
@@ -90,6 +90,7 @@ def lib():
         L.llsr_kernel_times_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.llsr_kernel_name.restype = C.c_char_p
         L.llsr_kernel_name.argtypes = [C.c_int32]
+        L.llsr_row_bins.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]
         L.llsr_set_profiling.argtypes = [C.c_void_p, C.c_int32]
         L.llsr_scan2map_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 5
         L.llsr_scan2map_batch.argtypes = [C.c_void_p, C.POINTER(_abi.S2MBatch), C.c_void_p]
@@ -175,7 +176,8 @@ def lib():
 
 def default_config(lidar: str, horizontal: int | None = None) -> Config:
     c = Config()
-    code = {"vlp16": _abi.LLSR_LIDAR_VLP16, "hdl64e": _abi.LLSR_LIDAR_HDL64E}[lidar]
+    code = {"vlp16": _abi.LLSR_LIDAR_VLP16, "vlp32c": _abi.LLSR_LIDAR_VLP32C,
+            "hdl64e": _abi.LLSR_LIDAR_HDL64E}[lidar]
     rc = lib().llsr_config_default(C.byref(c), code)
     if rc != 0:
         raise LlsrError(f"llsr_config_default: {rc}")
@@ -274,6 +276,14 @@ class Pipeline:
             self._check(n, "llsr_kernel_times_ms")
         return {lib().llsr_kernel_name(k).decode(): float(buf[k]) for k in range(n)}
 
+    def row_bins(self, b: int = 0) -> np.ndarray:
+        """use_vlp32c handles: slot b's vertical_raw2 of the last batch (llsr_row_bins), the ascending
+        distinct elevation bins observed in the scan; more than num_vertical_scans of them means
+        the scan overflowed and its points of rank >= H were dropped."""
+        bins = np.zeros(512, dtype=np.int32)
+        n = C.c_int32(0)
+        self._check(lib().llsr_row_bins(self._h, b, C.byref(n), bins.ctypes.data, bins.size), "llsr_row_bins")
+        return bins[: n.value].copy()
 
     # ---- scan-to-map (MapOptimization) -------------------------------------------------------
     def scan2map_reserve(self, problems: int, corner_map: int, surf_map: int, corner_q: int, surf_q: int):
@@ -679,12 +689,13 @@ class ImageProjection:
 
 def map_config(lidar: str | None = None, **kw) -> _abi.MapConfig:
     """llsr_map_config_default (lidar None) or the loam_config.yaml block of `lidar`
-    (llsr_map_config_lidar: "hdl64e" enables the loop-closure local map), then the overrides."""
+    (llsr_map_config_lidar: "vlp32c" and "hdl64e" enable the loop-closure local map), then the overrides."""
     c = _abi.MapConfig()
     if lidar is None:
         lib().llsr_map_config_default(C.byref(c))
     else:
-        code = {"vlp16": _abi.LLSR_LIDAR_VLP16, "hdl64e": _abi.LLSR_LIDAR_HDL64E}[lidar]
+        code = {"vlp16": _abi.LLSR_LIDAR_VLP16, "vlp32c": _abi.LLSR_LIDAR_VLP32C,
+                "hdl64e": _abi.LLSR_LIDAR_HDL64E}[lidar]
         if lib().llsr_map_config_lidar(C.byref(c), code) != 0:
             raise LlsrError("llsr_map_config_lidar failed")
     for k, v in kw.items():

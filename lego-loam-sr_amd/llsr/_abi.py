@@ -8,7 +8,9 @@ import numpy as np
 ABI_VERSION = 2  # LLSR_ABI_VERSION of include/llsr.h these bindings mirror (checked at load)
 LLSR_OK = 0
 LLSR_ERANGE = -34
+LLSR_EINVAL = -22
 LLSR_LIDAR_VLP16 = 0
+LLSR_LIDAR_VLP32C = 1
 LLSR_LIDAR_HDL64E = 2
 LLSR_MODE_FAITHFUL = 0
 LLSR_MODE_LM_APPLIED = 1
@@ -46,7 +48,7 @@ class Config(C.Structure):
 
 
 def config_for(lidar: str, horizontal: int | None = None) -> Config:
-    """The loam_config.yaml block (VLP-16: lines 1-67, HDL-64E: 137-203) as a Config.
+    """The loam_config.yaml block (VLP-16: lines 1-67, VLP-32c: 69-135, HDL-64E: 137-203) as a Config.
 
     Pure-Python copy of llsr_config_default so the oracle can be configured without the
     product library; tests check both agree.
@@ -58,6 +60,12 @@ def config_for(lidar: str, horizontal: int | None = None) -> Config:
         c.ground_scan_index, c.use_kitti = 7, 0
         c.DBFr, c.RatioXY, c.RatioZ = 5.0, 0.5, 2.5
         c.edge_threshold, c.surf_threshold, c.nearest_feature_search_distance = 0.03, 0.03, 5.0
+    elif lidar == "vlp32c":  # lines 69-135
+        c.num_vertical_scans, c.num_horizontal_scans = 32, 1800
+        c.vertical_angle_bottom, c.vertical_angle_top = -25.0, 15.0
+        c.ground_scan_index, c.use_kitti = 7, 0
+        c.DBFr, c.RatioXY, c.RatioZ = 5.0, 0.5, 2.5
+        c.edge_threshold, c.surf_threshold, c.nearest_feature_search_distance = 0.005, 0.005, 5.0
     elif lidar == "hdl64e":
         c.num_vertical_scans, c.num_horizontal_scans = 64, 1800
         c.vertical_angle_bottom, c.vertical_angle_top = -24.8, 2.0
@@ -69,11 +77,11 @@ def config_for(lidar: str, horizontal: int | None = None) -> Config:
     if horizontal is not None:
         c.num_horizontal_scans = horizontal
     c.sensor_mount_angle = 0.0
-    c.use_vlp32c = 0
+    c.use_vlp32c = 1 if lidar == "vlp32c" else 0
     c.segment_theta, c.segment_valid_point_num, c.segment_valid_line_num = 60.0, 5, 3
     c.scan_period = 0.1
     c.mapping_frequency_divider = 1
-    c.iterCountThres, c.step_size, c.stop_thres = 200, 1.0, 0.05
+    c.iterCountThres, c.step_size, c.stop_thres = (50 if lidar == "vlp32c" else 200), 1.0, 0.05
     c.mode = LLSR_MODE_FAITHFUL
     return c
 

@@ -20,13 +20,35 @@ import numpy as np
 VLP16 = "vlp16"
 HDL64E = "hdl64e"
 
+VLP32C = "vlp32c"
+VLP32C_UNIFORM = "vlp32c_uniform"
+
 _VLP16_FIRING = np.array([-15, 1, -13, 3, -11, 5, -9, 7, -7, 9, -5, 11, -3, 13, -1, 15], dtype=np.float64)
+# the VLP-32C's non-uniform elevation table, in firing order
+_VLP32C_FIRING = np.array([-25, -1, -1.667, -15.639, -11.31, 0, -0.667, -8.843, -7.254, 0.333, -0.333, -6.148,
+                           -5.333, 1.333, 0.667, -4, -4.667, 1.667, 1, -3.667, -3.333, 3.333, 2.333, -2.667,
+                           -3, 7, 4.667, -2.333, -2, 15, 10.333, -1.333], dtype=np.float64)
 
 
 def beam_layout(lidar: str):
-    """Return (elevations_deg in firing order, num_columns)."""
+    """Return (elevations_deg in firing order, num_columns).
+
+    "vlp32c": the VLP-32C's own elevations. With ang_bottom = 25.1 deg they fall into 32 distinct
+    0.335 deg bins of the use_vlp32c projection (IP:356); the tightest, -5.333 deg, sits 0.005 bin
+    (3e-5 rad) from a bin edge, far above the direction error of float32 points.
+    "vlp32c_uniform": 32 rings evenly spaced like -25..15 deg, fired low / high interleaved. The
+    plain branch's row (value r + 0.10) and the rank of the ring's bin coincide when every ring is
+    present. Exactly on -25..15 the ring at 12.42 deg would sit 0.002 bin from a bin edge, so the
+    whole layout is shifted up by 0.03 deg: every ring is then 0.015 bin (9e-5 rad) or more from one.
+    """
     if lidar == VLP16:
         return _VLP16_FIRING.copy(), 1800
+    if lidar == VLP32C:
+        return _VLP32C_FIRING.copy(), 1800
+    if lidar == VLP32C_UNIFORM:
+        elev = -25.0 + 0.03 + (15.0 - (-25.0)) / 31.0 * np.arange(32, dtype=np.float64)
+        order = np.stack([np.arange(0, 16), np.arange(16, 32)], axis=1).reshape(-1)
+        return elev[order], 1800
     if lidar == HDL64E:
         res = (2.0 - (-24.8)) / 63.0
         elev = -24.8 + res * np.arange(64, dtype=np.float64)
@@ -37,10 +59,22 @@ def beam_layout(lidar: str):
 
 
 class _Scene:
-    def __init__(self, rng: np.random.Generator, ground_ramp: tuple[float, float] | None = None):
+    def __init__(self, rng: np.random.Generator, ground_ramp: tuple[float, float] | None = None,
+                 hall: float | None = None):
         # ground_ramp = (x0, slope): beyond x = x0 the ground rises with this slope (a second plane
         # the near-ground RANSAC can lock onto, tests/test_gpu_features_ties.py)
         self.ramp = ground_ramp
+        self.ground_z = -1.3
+        if hall is not None:
+            # flat ground inside four vertical walls at +-hall m, nothing else: with the walls beyond
+            # the lower rings' ground hits, every ground-to-wall step falls into the upper rows
+            # (tests/test_gpu_vlp32c.py)
+            self.boxes = np.array([(hall, hall + 1.0, -hall - 1.0, hall + 1.0, -1.3, 30.0),
+                                   (-hall - 1.0, -hall, -hall - 1.0, hall + 1.0, -1.3, 30.0),
+                                   (-hall - 1.0, hall + 1.0, hall, hall + 1.0, -1.3, 30.0),
+                                   (-hall - 1.0, hall + 1.0, -hall - 1.0, -hall, -1.3, 30.0)], dtype=np.float64)
+            self.cyl = np.zeros((0, 5), dtype=np.float64)
+            return
         boxes = []  # (xmin, xmax, ymin, ymax, zmin, zmax)
         # facades: left y in [9, 12], right y in [-14, -11], long along x
         for side, y0, y1 in ((1, 9.0, 12.0), (-1, -14.0, -11.0)):
@@ -80,7 +114,6 @@ class _Scene:
             for x in np.arange(-55.0, 80.0, rng.uniform(14.0, 20.0)):  # tree trunks
                 cyl.append((x + rng.uniform(-2, 2), side * rng.uniform(7.8, 8.6), rng.uniform(0.2, 0.35), -1.3, 3.0))
         self.cyl = np.array(cyl, dtype=np.float64)
-        self.ground_z = -1.3
 
     def cast(self, o: np.ndarray, d: np.ndarray, tmax: float) -> np.ndarray:
         """Nearest hit distance along unit rays d from origin o (inf = miss)."""
@@ -148,17 +181,18 @@ def _rot_zyx(roll: float, pitch: float, yaw: float) -> np.ndarray:
 def make_scan(seed: int, lidar: str = VLP16, dropout: float = 0.02, noise: float = 0.01,
               max_range: float = 100.0, origin_xy: tuple[float, float] | None = None,
               scene_id: int | None = None, ground_ramp: tuple[float, float] | None = None,
-              motion: bool = False) -> np.ndarray:
+              motion: bool = False, hall: float | None = None) -> np.ndarray:
     """One raw scan as float32 [N, 4] (x, y, z, intensity), N = rings * columns (NaNs kept).
 
     The sensor sits at (0.5 * (seed % 64), U(-0.5, 0.5), 0) of scene `seed // 64`; scan-to-map
     fixtures override both (`origin_xy`, `scene_id`) to place keyframes along one street. With
     `motion` the sensor also carries the drive's 6-DoF attitude (`sensor_attitude`): the rays are
     cast in the world from the tilted, yawed sensor and the points are returned in the sensor's own
-    frame, so every beam still points at its range-image bin centre."""
+    frame, so every beam still points at its range-image bin centre.
+    `hall` replaces the street by flat ground inside four vertical walls at +-hall m."""
     rng = np.random.default_rng(seed)
     scene_id = seed // 64 if scene_id is None else scene_id  # scenes shared by 64 scans
-    scene = _Scene(np.random.default_rng(1000003 + scene_id), ground_ramp)
+    scene = _Scene(np.random.default_rng(1000003 + scene_id), ground_ramp, hall)
     elev, W = beam_layout(lidar)
     H = elev.shape[0]
     res_x = 2.0 * np.pi / W

@@ -2,7 +2,7 @@
 kernels of each batch, llsr_kernel_times_ms) and phase attribution of selected kernels by
 early-exit re-launches (llsr_debug_phase_ms; diagnostic launches, outputs meaningless).
 
-    python scripts/kprof.py [vlp16|hdl64e] [B]
+    python scripts/kprof.py [vlp16|vlp32c|hdl64e] [B]
 """
 import json
 import os
