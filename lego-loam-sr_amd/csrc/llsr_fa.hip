@@ -837,7 +837,7 @@ __global__ __launch_bounds__(256, 5) void k_select_ring(DevCfg c, DevBufs d) {
 // them: k_vox_top partitions a ring block-wide while its ranges are above kBsBig and lists the
 // ranges that remain; k_vox_leaf finishes every listed range with one wave, the ranges of all rings
 // and scans as one pool of work items (a ring's few ranges differ widely in cost, so waves tied
-// to one ring wait for its longest); k_vox_sum builds the centroids.
+// to one ring wait for its longest); k_vox_sum builds the centroids, one lane per voxel.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t* vox_keys(const DevCfg& c, const DevBufs& d, int slot) {
   return reinterpret_cast<uint32_t*>(d.ccl_a + (size_t)(slot / c.H) * c.HW) + d.start_ring[slot];
@@ -923,6 +923,7 @@ __global__ __launch_bounds__(64, 8) void k_vox_leaf(DevCfg c, DevBufs d, VoxRang
 
 // grid (H, B), block 256: the centroids of a pending ring from its sorted keys; publishes the
 // ring's less-flat count.
+constexpr int kVoxSumBatch = 4;  // point loads a lane keeps in flight ahead of its adds
 __global__ __launch_bounds__(256, 8) void k_vox_sum(DevCfg c, DevBufs d) {
   __shared__ uint32_t key[kRingMax];
   __shared__ uint16_t cpos[kRingMax];
@@ -948,13 +949,16 @@ __global__ __launch_bounds__(256, 8) void k_vox_sum(DevCfg c, DevBufs d) {
   const int wv = tid >> 6, ln = lane_id();
   const unsigned long long ltm = (1ull << ln) - 1ull;
   // voxel heads in sorted order; sorted position t = u * 256 + tid sits in slot u of a lane, so a
-  // wave's heads of one slot are consecutive voxels and their centroids are stored contiguously;
-  // output positions come from per-(slot, wave) ballot counts scanned in (slot, wave) = sorted order.
+  // wave's heads of one slot are consecutive voxels; output positions come from per-(slot, wave)
+  // ballot counts scanned in (slot, wave) = sorted order.
   unsigned long long mH[kLp];
+  int pq[kLp];  // the ring position of the point at sorted position t
 #pragma unroll
   for (int u = 0; u < kLp; ++u) {
     const int t = u * 256 + tid;
-    const bool head = t < L && (t == 0 || (key[t] >> 11) != (key[t - 1] >> 11));
+    const uint32_t kt = t < L ? key[t] : 0u;
+    const bool head = t < L && (t == 0 || (kt >> 11) != (key[t - 1] >> 11));
+    pq[u] = t < L ? (int)cpos[kt & 0x7ffu] : 0;
     mH[u] = __ballot(head);
     if (ln == 0) scnt[u * 4 + wv] = (int)__popcll(mH[u]);
   }
@@ -967,20 +971,46 @@ __global__ __launch_bounds__(256, 8) void k_vox_sum(DevCfg c, DevBufs d) {
   }
   __syncthreads();
   const int V = scnt[kLp * 4];
+  // The keys are dead (every read of key[] is above the barriers): their storage now lists the
+  // points' ring positions in sorted order (spos) and the sorted position at which each voxel
+  // starts (vstart, by output position), so a voxel's run is known before its first point load.
+  uint16_t* spos = reinterpret_cast<uint16_t*>(key);
+  uint16_t* vstart = spos + kRingMax;
 #pragma unroll
   for (int u = 0; u < kLp; ++u) {
     const int t = u * 256 + tid;
-    if (!((mH[u] >> ln) & 1ull)) continue;
-    const uint32_t vr = key[t] >> 11;
+    if (t < L) spos[t] = (uint16_t)pq[u];
+    if ((mH[u] >> ln) & 1ull) vstart[scnt[u * 4 + wv] + (int)__popcll(mH[u] & ltm)] = (uint16_t)t;
+  }
+  __syncthreads();
+  // One lane per voxel, in output order (stores of a wave are contiguous). The loads of a run go
+  // out kVoxSumBatch at a time, the next batch before the current one is added, so no add waits for a
+  // load of its own step; the adds stay in sorted order, one point after the other.
+  for (int v = tid; v < V; v += 256) {
+    const int t = vstart[v], e = v + 1 < V ? (int)vstart[v + 1] : L;
     float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-    int e = t;
-    for (; e < L && (key[e] >> 11) == vr; ++e) {
-      const float4 p = lp[cpos[key[e] & 0x7ffu]];
-      sx += p.x; sy += p.y; sz += p.z; si += p.w;
+    auto point = [&](int q) {  // the point at sorted position q of the run
+      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (q < e) r = lp[spos[q]];
+      return r;
+    };
+    float4 p[kVoxSumBatch];
+#pragma unroll
+    for (int j = 0; j < kVoxSumBatch; ++j) p[j] = point(t + j);
+    for (int q = t; q < e; q += kVoxSumBatch) {
+      float4 nx[kVoxSumBatch];
+#pragma unroll
+      for (int j = 0; j < kVoxSumBatch; ++j) nx[j] = point(q + kVoxSumBatch + j);
+#pragma unroll
+      for (int j = 0; j < kVoxSumBatch; ++j)
+        if (q + j < e) {
+          sx += p[j].x; sy += p[j].y; sz += p[j].z; si += p[j].w;
+        }
+#pragma unroll
+      for (int j = 0; j < kVoxSumBatch; ++j) p[j] = nx[j];
     }
     const float nn = (float)(e - t);
-    const int vo = scnt[u * 4 + wv] + (int)__popcll(mH[u] & ltm);
-    out[vo] = make_float4(sx / nn, sy / nn, sz / nn, si / nn);
+    out[v] = make_float4(sx / nn, sy / nn, sz / nn, si / nn);
   }
   if (tid == 0) rc[2 * H + i] = V;
 }
