@@ -561,6 +561,55 @@ int32_t llsr_map_save(llsr_map* m, float* d_corner, int64_t cap_corner, float* d
 int32_t llsr_keypose_radius_sorted(const float* poses4, int32_t K, const float pos[3], float radius,
                                    int32_t* out_idx);
 
+/* ---- Loop closure: detectLoopClosure / performLoopClosure (MO:894-1094), correctPoses (MO:1757-1785) ----
+ * The host side of the reference's loop-closure thread (started at the commented-out MO:174) and the
+ * store's half of it: keyframe times, the candidate selection, one ICP iteration's rigid estimate,
+ * the pose constraint, and the corrected poses coming back. DESIGN.md §16 is the specification of the
+ * whole path (PCL and Eigen are restated, not linked); the device alignment itself — submap assembly,
+ * correspondences, the ICP loop and the fitness score on the keyframe store — is not in the library
+ * yet, so a node still runs pcl::IterativeClosestPoint between llsr_loop_candidate and
+ * llsr_loop_constraint. The BetweenFactor and iSAM2 stay in the node. */
+typedef struct llsr_loop_config {
+  float search_radius;     /* history_keyframe_search_radius (CFG:29 / 97 / 165) */
+  int32_t search_num;      /* history_keyframe_search_num (CFG:30 / 98 / 166) */
+  float fitness_score;     /* history_keyframe_fitness_score (CFG:31 / 99 / 167) */
+  float leaf;              /* downSizeFilterHistoryKeyFrames (MO:97) */
+  double min_time_gap;     /* 30.0 s (MO:912) */
+  int32_t icp_max_iterations;               /* 100 (MO:1001) */
+  int32_t pad;
+  double icp_transformation_epsilon;        /* 1e-6 (MO:1002) */
+  double icp_fitness_epsilon;               /* 1e-6 (MO:1008) */
+  double icp_max_correspondence_distance;   /* 100 (MO:1007) */
+} llsr_loop_config;
+/* The block of loam_config.yaml for `lidar` (VLP-16: 15 m, 50, 0.5; VLP-32c: 50 m, 40, 1.5;
+ * HDL-64E: 30 m, 30, 0.8) and the constants of MO:97, 912, 1001-1008. */
+int32_t llsr_loop_config_lidar(llsr_loop_config* cfg, int32_t lidar);
+/* cloudKeyPoses6D[index].time in seconds (timeLaserOdometry of the keyframe's scan, MO:1709). A
+ * keyframe whose time was never set holds NaN: fabs(NaN - now) > gap is false, so it is never a loop
+ * candidate. llsr_map_keyframe_times copies the times of keyframes 0 .. min(cap, K) - 1 and returns K. */
+int32_t llsr_map_set_keyframe_time(llsr_map* m, int32_t index, double seconds);
+int32_t llsr_map_keyframe_times(const llsr_map* m, double* out, int32_t cap);
+/* correctPoses (MO:1757-1785): overwrite the first n key poses (x, y, z, roll, pitch, yaw each, the
+ * store's layout; the node applies the GTSAM axis remap of MO:1765-1780) and clear the recent-
+ * keyframe queue (MO:1759-1761) and the radius branch's keyframe list, so the next llsr_map_extract
+ * with enable_loop_closure refills from the newest keyframe backwards with the new poses; the global
+ * map and llsr_map_save read the new poses too. LLSR_ERANGE when n exceeds the keyframe count. */
+int32_t llsr_map_set_key_poses(llsr_map* m, const float* poses6, int32_t n);
+/* Host-only (no device). The candidate of detectLoopClosure (MO:902-919) over K poses (x, y, z,
+ * anything) and times[K]: the sorted radius search of llsr_keypose_radius_sorted, then the first hit
+ * with fabs(times[k] - now) > gap in double; the keyframe index or -1. */
+int32_t llsr_loop_candidate(const float* poses4, const double* times, int32_t K, const float pos[3], double now,
+                            float radius, double gap);
+/* Eigen::umeyama without scaling of n >= 1 correspondences src_xyz[3n] -> dst_xyz[3n]
+ * into the row-major 4x4 T16: what one ICP iteration estimates. */
+int32_t llsr_umeyama3(const float* src_xyz, const float* dst_xyz, int32_t n, float* T16);
+/* The pose constraint of MO:1056-1081 from the ICP transformation, the latest and the closest key
+ * pose (x, y, z, roll, pitch, yaw each) and the fitness score: pose_from = x, y, z, roll, pitch, yaw
+ * of tCorrect (MO:1072), pose_to = z, x, y, yaw, roll, pitch of the closest key pose (MO:1076),
+ * *variance = (float)fitness for all six variances (MO:1078-1081). */
+int32_t llsr_loop_constraint(const float* T16, const float* pose_latest6, const float* pose_closest6, double fitness,
+                             float* pose_from6, float* pose_to6, float* variance);
+
 /* ---- Mapping chain: ImageProjection -> FeatureAssociation -> MapOptimization::run ----
  * (mapOptmization.cpp:1854-1896.) Each llsr_mapping_batch call runs llsr_odometry_batch on the B
  * slots and then, for every slot that sends an AssociationOut this frame — FA counts the frames

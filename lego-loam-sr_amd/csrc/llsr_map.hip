@@ -438,7 +438,7 @@ struct llsr_map {
   // keyframe store: packed points, host-side index
   float4* store = nullptr;
   size_t store_cap = 0, store_used = 0;
-  struct Kf { float pose[6]; long long off[3]; int n[3]; };  // corner, surf, outlier
+  struct Kf { float pose[6]; long long off[3]; int n[3]; double time; };  // corner, surf, outlier; time NaN until set
   std::vector<Kf> kf;
   // the local map's keyframe list: surroundingExistingKeyPosesID (radius branch) or the indices of
   // recent{Corner,Surf,Outlier}CloudKeyFrames, oldest first (loop-closure branch); with the
@@ -800,6 +800,7 @@ extern "C" int32_t llsr_map_add_keyframe(llsr_map* m, const float pose[6], const
   }
   llsr_map::Kf k{};
   std::memcpy(k.pose, pose, sizeof k.pose);
+  k.time = std::nan("");
   const float* src[3] = {c, su, o};
   const int cnt[3] = {nc, ns, no};
   for (int a = 0; a < 3; ++a) {
@@ -1221,5 +1222,30 @@ extern "C" int32_t llsr_map_save(llsr_map* m, float* d_corner, int64_t cap_corne
   rc = gm_voxel(m, tot[1], m->cfg.surf_leaf, reinterpret_cast<float4*>(d_surf), cap_surf, n_surf, nullptr, s);
   if (rc != LLSR_OK) return rc;
   MAP_OK(m, hipStreamSynchronize(s));
+  return LLSR_OK;
+}
+
+// ---- loop closure: the keyframe times of detectLoopClosure (MO:912) and correctPoses (MO:1757-1785) ----
+extern "C" int32_t llsr_map_set_keyframe_time(llsr_map* m, int32_t index, double seconds) {
+  if (!m) return LLSR_EINVAL;
+  if (index < 0 || index >= (int32_t)m->kf.size()) return mfail(m, LLSR_ERANGE, "set_keyframe_time: no such keyframe");
+  m->kf[index].time = seconds;
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_map_keyframe_times(const llsr_map* m, double* out, int32_t cap) {
+  if (!m || cap < 0 || (cap > 0 && !out)) return LLSR_EINVAL;
+  const int n = (int)m->kf.size();
+  for (int k = 0; k < n && k < cap; ++k) out[k] = m->kf[k].time;
+  return n;
+}
+
+extern "C" int32_t llsr_map_set_key_poses(llsr_map* m, const float* poses6, int32_t n) {
+  if (!m || n < 0 || (n > 0 && !poses6)) return mfail(m, LLSR_EINVAL, "set_key_poses: bad arguments");
+  if (n > (int32_t)m->kf.size()) return mfail(m, LLSR_ERANGE, "set_key_poses: more poses than keyframes");
+  for (int32_t k = 0; k < n; ++k) std::memcpy(m->kf[k].pose, poses6 + 6 * (size_t)k, sizeof m->kf[k].pose);
+  // MO:1759-1761: the queue of transformed recent keyframes goes; latestFrameID stays. The store
+  // keeps keyframes in their own frames, so nothing else was transformed with the old poses.
+  m->sel.ids.clear();
   return LLSR_OK;
 }

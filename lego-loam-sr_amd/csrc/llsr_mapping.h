@@ -24,7 +24,7 @@ namespace llsr_mapping {
 // indices rather than the transformed clouds of MO:1115-1143: a key pose never changes after
 // saveKeyFramesAndFactor stores it (correctPoses acts only after a closed loop, MO:1758, and the
 // loop-closure thread is commented out, MO:174), so transforming at extract time gives the same
-// points.
+// points. correctPoses itself (llsr_map_set_key_poses) clears the queue, as MO:1759-1761 does.
 struct MapSel {
   std::vector<int> ids;
   int latest_frame_id = 0;

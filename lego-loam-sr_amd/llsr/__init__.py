@@ -48,6 +48,8 @@ EXPORTS = [
     "llsr_update_initial_guess", "llsr_odometry_batch_odom", "llsr_odometry_fetch_lm", "llsr_mapping_batch_odom",
     "llsr_global_map_config_default", "llsr_map_global", "llsr_map_save", "llsr_keypose_radius_sorted",
     "llsr_mapping_global_map", "llsr_mapping_save_map", "llsr_row_bins",
+    "llsr_loop_config_lidar", "llsr_map_set_keyframe_time", "llsr_map_keyframe_times",
+    "llsr_map_set_key_poses", "llsr_loop_candidate", "llsr_umeyama3", "llsr_loop_constraint",
 ]
 
 
@@ -149,6 +151,15 @@ def lib():
         L.llsr_map_save.argtypes = [C.c_void_p] + _save
         L.llsr_mapping_save_map.argtypes = [C.c_void_p, C.c_int32] + _save
         L.llsr_keypose_radius_sorted.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p]
+        L.llsr_loop_config_lidar.argtypes = [C.POINTER(_abi.LoopConfig), C.c_int32]
+        L.llsr_map_set_keyframe_time.argtypes = [C.c_void_p, C.c_int32, C.c_double]
+        L.llsr_map_keyframe_times.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.llsr_map_set_key_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.llsr_loop_candidate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_float,
+                                          C.c_double]
+        L.llsr_umeyama3.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.llsr_loop_constraint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]
         L.llsr_mapping_init.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.MapConfig)]
         L.llsr_mapping_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.llsr_mapping_fetch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.MappingSlot)]
@@ -726,6 +737,61 @@ def keypose_radius_sorted(poses4, pos, radius: float) -> np.ndarray:
     return out[:n].copy()
 
 
+def loop_config(lidar: str = "hdl64e", **kw) -> _abi.LoopConfig:
+    """llsr_loop_config_lidar: the loop-closure parameters of the loam_config.yaml block of `lidar`
+    (history_keyframe_search_radius / _search_num / _fitness_score) with the constants of
+    performLoopClosure (MO:97, 912, 1001-1008), then the overrides."""
+    c = _abi.LoopConfig()
+    code = {"vlp16": _abi.LLSR_LIDAR_VLP16, "vlp32c": _abi.LLSR_LIDAR_VLP32C, "hdl64e": _abi.LLSR_LIDAR_HDL64E}[lidar]
+    if lib().llsr_loop_config_lidar(C.byref(c), code) != 0:
+        raise LlsrError("llsr_loop_config_lidar failed")
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def loop_candidate(poses4, times, pos, now: float, radius: float, gap: float = 30.0) -> int:
+    """detectLoopClosure's candidate (llsr_loop_candidate, host only): the first key pose of the
+    sorted radius search with fabs(time - now) > gap, or -1."""
+    p = np.ascontiguousarray(poses4, np.float32).reshape(-1, 4)
+    t = np.ascontiguousarray(times, np.float64).reshape(-1)
+    if len(t) != len(p):
+        raise ValueError("one time per pose")
+    q = np.ascontiguousarray(pos, np.float32)
+    r = lib().llsr_loop_candidate(p.ctypes.data, t.ctypes.data, len(p), q.ctypes.data, now, radius, gap)
+    if r < -1:
+        raise LlsrError(f"llsr_loop_candidate: {r}")
+    return r
+
+
+def umeyama3(src_xyz, dst_xyz) -> np.ndarray:
+    """One ICP iteration's rigid estimate (llsr_umeyama3, host only): the 4x4 float32 T with
+    dst ~ T src, Eigen::umeyama without scaling in the order DESIGN.md §16 fixes."""
+    a = np.ascontiguousarray(src_xyz, np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(dst_xyz, np.float32).reshape(-1, 3)
+    if len(a) != len(b):
+        raise ValueError("one destination per source point")
+    T = np.zeros(16, np.float32)
+    rc = lib().llsr_umeyama3(a.ctypes.data, b.ctypes.data, len(a), T.ctypes.data)
+    if rc != 0:
+        raise LlsrError(f"llsr_umeyama3: {rc}")
+    return T.reshape(4, 4)
+
+
+def loop_constraint(T, pose_latest, pose_closest, fitness: float):
+    """performLoopClosure's pose constraint (llsr_loop_constraint, host only; MO:1056-1081):
+    (pose_from, pose_to, noise_variance) for BetweenFactor(latest, closest, from.between(to))."""
+    t = np.ascontiguousarray(T, np.float32).reshape(16)
+    a = np.ascontiguousarray(pose_latest, np.float32).reshape(6)
+    b = np.ascontiguousarray(pose_closest, np.float32).reshape(6)
+    pf, pt, var = np.zeros(6, np.float32), np.zeros(6, np.float32), C.c_float()
+    rc = lib().llsr_loop_constraint(t.ctypes.data, a.ctypes.data, b.ctypes.data, fitness, pf.ctypes.data,
+                                    pt.ctypes.data, C.byref(var))
+    if rc != 0:
+        raise LlsrError(f"llsr_loop_constraint: {rc}")
+    return pf, pt, var.value
+
+
 def _global_map(torch, device, call, caps, edge: bool, planar: bool) -> dict:
     """Run a llsr_map_global-shaped call with output buffers of caps[global, edge, planar] points,
     growing them once to the reported sizes on LLSR_ERANGE."""
@@ -900,6 +966,23 @@ class LocalMap:
         self._check(rc, "llsr_map_save")
         self._leave()
         return c, su
+
+    def set_keyframe_time(self, index: int, seconds: float):
+        """cloudKeyPoses6D[index].time (llsr_map_set_keyframe_time); unset times never match a loop."""
+        self._check(lib().llsr_map_set_keyframe_time(self._m, index, seconds), "llsr_map_set_keyframe_time")
+
+    def set_key_poses(self, poses6):
+        """correctPoses (MO:1757-1785, llsr_map_set_key_poses): overwrite the first len(poses6) key poses
+        (x, y, z, roll, pitch, yaw) and drop the recent-keyframe queue."""
+        p = np.ascontiguousarray(poses6, np.float32).reshape(-1, 6)
+        self._check(lib().llsr_map_set_key_poses(self._m, p.ctypes.data, len(p)), "llsr_map_set_key_poses")
+
+    def keyframe_times(self) -> np.ndarray:
+        """cloudKeyPoses6D[*].time (llsr_map_keyframe_times): NaN where no time was set."""
+        n = self._check(lib().llsr_map_keyframe_times(self._m, None, 0), "llsr_map_keyframe_times")
+        out = np.zeros(max(n, 1), np.float64)
+        lib().llsr_map_keyframe_times(self._m, out.ctypes.data, n)
+        return out[:n]
 
     def keyframe_ids(self) -> np.ndarray:
         n = lib().llsr_map_keyframe_ids(self._m, None, 0)

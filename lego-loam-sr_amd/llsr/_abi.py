@@ -293,6 +293,14 @@ class GlobalMapReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LoopConfig(C.Structure):
+    """llsr_loop_config (include/llsr.h): detectLoopClosure / performLoopClosure parameters."""
+    _fields_ = [("search_radius", C.c_float), ("search_num", C.c_int32), ("fitness_score", C.c_float),
+                ("leaf", C.c_float), ("min_time_gap", C.c_double), ("icp_max_iterations", C.c_int32),
+                ("pad", C.c_int32), ("icp_transformation_epsilon", C.c_double), ("icp_fitness_epsilon", C.c_double),
+                ("icp_max_correspondence_distance", C.c_double)]
+
+
 class MappingSlot(C.Structure):
     """llsr_mapping_slot (include/llsr.h): one sequence's MapOptimization state after the last call."""
     _fields_ = [("frames", C.c_int32), ("mo_frames", C.c_int32), ("keyframes", C.c_int32), ("lm_ran", C.c_int32),
