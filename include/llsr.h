@@ -562,13 +562,12 @@ int32_t llsr_keypose_radius_sorted(const float* poses4, int32_t K, const float p
                                    int32_t* out_idx);
 
 /* ---- Loop closure: detectLoopClosure / performLoopClosure (MO:894-1094), correctPoses (MO:1757-1785) ----
- * The host side of the reference's loop-closure thread (started at the commented-out MO:174) and the
- * store's half of it: keyframe times, the candidate selection, one ICP iteration's rigid estimate,
- * the pose constraint, and the corrected poses coming back. DESIGN.md §16 is the specification of the
- * whole path (PCL and Eigen are restated, not linked); the device alignment itself — submap assembly,
- * correspondences, the ICP loop and the fitness score on the keyframe store — is not in the library
- * yet, so a node still runs pcl::IterativeClosestPoint between llsr_loop_candidate and
- * llsr_loop_constraint. The BetweenFactor and iSAM2 stay in the node. */
+ * The reference's loop-closure thread (started at the commented-out MO:174) up to the factor graph:
+ * keyframe times, the candidate selection, the two submaps on the keyframe store, the ICP alignment on
+ * the device (llsr_icp_align) and on the host (llsr_icp_align_host), the acceptance test, the pose
+ * constraint, and the corrected poses coming back. llsr_map_loop_closure runs all of it in one call;
+ * the pieces are entry points of their own. DESIGN.md §16 is the specification of the whole path (PCL
+ * and Eigen are restated, not linked). The BetweenFactor and iSAM2 stay in the node. */
 typedef struct llsr_loop_config {
   float search_radius;     /* history_keyframe_search_radius (CFG:29 / 97 / 165) */
   int32_t search_num;      /* history_keyframe_search_num (CFG:30 / 98 / 166) */
@@ -609,6 +608,78 @@ int32_t llsr_umeyama3(const float* src_xyz, const float* dst_xyz, int32_t n, flo
  * *variance = (float)fitness for all six variances (MO:1078-1081). */
 int32_t llsr_loop_constraint(const float* T16, const float* pose_latest6, const float* pose_closest6, double fitness,
                              float* pose_from6, float* pose_to6, float* variance);
+/* The alignment itself: pcl::IterativeClosestPoint with an identity guess (MO:1000-1017) as DESIGN.md
+ * §16 specifies it. Clouds are [n][4] floats (x, y, z, intensity). `state` is the convergence state:
+ * 0 none, 1 iterations, 2 transform, 3 absolute MSE, 4 relative MSE, 5 no correspondences (fewer
+ * than 3 pairs: converged 0, T keeps its value). A point that finds no target (a NaN or beyond
+ * +-1 048 000 m coordinate, an empty target) is in no pair and is not counted in the fitness mean;
+ * fitness is DBL_MAX when no point counts. */
+typedef struct llsr_icp_result {
+  int32_t converged;      /* hasConverged() */
+  int32_t state;          /* see above */
+  int32_t iterations;     /* completed iterations */
+  int32_t n_pairs_last;   /* correspondences kept in the last correspondence step */
+  double fitness;         /* getFitnessScore() of the source moved by T */
+  float T[16];            /* getFinalTransformation(), row-major 4x4 */
+} llsr_icp_result;
+#define LLSR_ICP_MAX_POINTS 100000000
+/* Host-only (no device), serial: the same loop bodies the device alignment runs, over heap buffers.
+ * aligned4 ([n_src][4], may be NULL) receives the source moved by T in one step (the pubIcpKeyFrames
+ * cloud); it must not overlap the inputs. Uses cfg's icp_* fields. */
+int32_t llsr_icp_align_host(const float* src4, int32_t n_src, const float* tgt4, int32_t n_tgt,
+                            const llsr_loop_config* cfg, llsr_icp_result* res, float* aligned4);
+/* The same alignment on device clouds (16-byte aligned, [n][4] floats). The workspace owns the
+ * target's cell grid and the loop's buffers and grows them on demand; one call at a time per
+ * workspace. d_aligned4 (device, [n_src][4], may be NULL) as above. The loop's state lives in device
+ * memory; the host reads one state word per iteration and the result at the end. Synchronises
+ * hip_stream (NULL: the workspace's own stream). llsr_icp_create returns NULL without a HIP device. */
+typedef struct llsr_icp llsr_icp;
+llsr_icp* llsr_icp_create(int32_t hip_device);
+void llsr_icp_destroy(llsr_icp* w);
+const char* llsr_icp_last_error(const llsr_icp* w);
+int32_t llsr_icp_align(llsr_icp* w, const float* d_src4, int32_t n_src, const float* d_tgt4, int32_t n_tgt,
+                       const llsr_loop_config* cfg, llsr_icp_result* res, float* d_aligned4, void* hip_stream);
+/* Diagnostic: HIP-event times of the last llsr_icp_align on w, in ms: the correspondence kernels and
+ * the solve kernels summed over the iterations, and the whole call's device time. */
+int32_t llsr_icp_last_times(const llsr_icp* w, float* corr_ms, float* solve_ms, float* total_ms);
+/* One detectLoopClosure + performLoopClosure on the keyframe store. */
+typedef struct llsr_loop_report {
+  int32_t found;            /* a candidate exists (0: an empty store or no candidate; nothing else is set) */
+  int32_t closest_id;       /* closestHistoryFrameID, -1 without a candidate */
+  int32_t latest_id;        /* latestFrameIDLoopCloure = the newest keyframe */
+  int32_t accepted;         /* converged && fitness <= fitness_score (MO:1038-1040) */
+  int64_t n_source;         /* latestSurfKeyFrameCloud after the intensity filter */
+  int64_t n_target;         /* nearHistorySurfKeyFrameCloud before the VoxelGrid */
+  int64_t n_source_ds;      /* both through downSizeFilterHistoryKeyFrames */
+  int64_t n_target_ds;
+  llsr_icp_result icp;      /* the alignment of the raw clouds (llsr_map_loop_closure only) */
+  float pose_from[6];       /* the constraint of llsr_loop_constraint, when accepted */
+  float pose_to[6];
+  float variance;
+  float ms;                 /* wall time of the call */
+} llsr_loop_report;
+/* The candidate (llsr_loop_candidate over the store's poses and times, robot_pos = currentRobotPosPoint,
+ * now = timeLaserOdometry) and the two submaps (MO:920-981): source = the newest keyframe's corner
+ * then surf cloud in the map frame, the points with (int)intensity >= 0 in order; target = keyframes
+ * closest - search_num .. closest + search_num inside the store, corner then surf each; both also
+ * through a VoxelGrid of cfg->leaf. Outputs are device float4 clouds with capacities in points, with
+ * the rules of llsr_map_global: a NULL output with capacity 0 is skipped and its size still reported;
+ * LLSR_ERANGE with the sizes in rep when a capacity is too small, nothing written, and a retry with
+ * larger buffers gives the identical result. Changes no map state. Synchronises hip_stream; uses the
+ * map's scratch, so it must not overlap another call on the same map. */
+int32_t llsr_map_loop_submaps(llsr_map* m, const llsr_loop_config* cfg, const float robot_pos[3], double now,
+                              llsr_loop_report* rep, float* d_source, int64_t cap_source, float* d_target,
+                              int64_t cap_target, float* d_source_ds, int64_t cap_sds, float* d_target_ds, int64_t cap_tds,
+                              void* hip_stream);
+/* llsr_map_loop_submaps, then llsr_icp_align of the raw source onto the raw target (MO:1011-1012) in
+ * the workspace w (NULL: one the map owns), the acceptance test and, when accepted, the constraint.
+ * d_aligned receives the source moved by the final transformation (pubIcpKeyFrames /
+ * pubIcpKeyFramesFalse) whether or not the result is accepted; d_target_ds the downsampled target
+ * (pubHistoryKeyFrames). The node adds the BetweenFactor, runs iSAM2 and hands the corrected poses
+ * back through llsr_map_set_key_poses. Same output, capacity, state and overlap rules as above. */
+int32_t llsr_map_loop_closure(llsr_map* m, llsr_icp* w, const llsr_loop_config* cfg, const float robot_pos[3],
+                              double now, llsr_loop_report* rep, float* d_aligned, int64_t cap_aligned,
+                              float* d_target_ds, int64_t cap_tds, void* hip_stream);
 
 /* ---- Mapping chain: ImageProjection -> FeatureAssociation -> MapOptimization::run ----
  * (mapOptmization.cpp:1854-1896.) Each llsr_mapping_batch call runs llsr_odometry_batch on the B

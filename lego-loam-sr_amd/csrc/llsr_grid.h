@@ -11,15 +11,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "llsr_cell.h"  // CellSlot, cell_coord, cell_key, cell_hash, grid_find, nn_before, grid_log2_table
+
 namespace llsr {
-
-struct CellSlot {
-  uint64_t key;  // packed cell or kCellEmpty
-  int start;     // first point of the cell in `sorted`
-  int count;
-};
-
-constexpr uint64_t kCellEmpty = ~0ull;
 
 struct CellGrid {
   const float4* src;    // the clouds, concatenated over the batch
@@ -43,52 +37,6 @@ struct CellGrids2 {
   int P;
 };
 
-__device__ __forceinline__ int cell_coord(float v) {
-  // floor() to a cell index; NaN / huge coordinates land in a far sentinel cell (their distance
-  // tests fail anyway, so where they are bucketed cannot change a result)
-  const float f = floorf(v);
-  return (f > -1048000.0f && f < 1048000.0f) ? (int)f : 1048500;
-}
-
-__device__ __forceinline__ uint64_t cell_key(int a, int b, int c) {
-  return ((uint64_t)(uint32_t)(a + 1048576) << 42) | ((uint64_t)(uint32_t)(b + 1048576) << 21) |
-         (uint64_t)(uint32_t)(c + 1048576);
-}
-
-__device__ __forceinline__ uint32_t cell_hash(uint64_t k, int log2T) {
-  return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> (64 - log2T));
-}
-
-// Probe for `key`; returns the slot or -1 (the table is never full: more slots than points).
-__device__ __forceinline__ int grid_find(const CellSlot* __restrict__ tab, int log2T, uint64_t key) {
-  const uint32_t mask = (1u << log2T) - 1u;
-  uint32_t s = cell_hash(key, log2T);
-  for (;;) {
-    const uint64_t k = tab[s].key;
-    if (k == key) return (int)s;
-    if (k == kCellEmpty) return -1;
-    s = (s + 1) & mask;
-  }
-}
-
-// (d, index) lexicographic order: the result of inserting candidates in index order with
-// nanoflann's strict '<' (KNNResultSet::addPoint).
-__device__ __forceinline__ bool nn_before(float da, int ia, float db, int ib) {
-  return da < db || (da == db && ia < ib);
-}
-
-// Table size for `cap` points per problem.
-// Table slots: the smallest power of two ABOVE the point capacity, so at least one slot stays
-// empty even if every point had its own cell (grid_find and the insert probes end at an empty
-// slot). Clouds hold several points per 1 m cell, so the load is low in practice; k_grid_clear and
-// k_grid_alloc sweep the whole table, so a 2x margin doubled their cost (measured: scan-to-map grid
-// build 3.7 ms per 256-problem step with 2x).
-inline int grid_log2_table(int cap) {
-  int l = 4;
-  while ((1ll << l) <= (long long)(cap > 1 ? cap : 1)) ++l;
-  return l;
-}
-
 __global__ void k_grid_clear(CellGrids2 g);
 __global__ void k_grid_insert(CellGrids2 g);
 __global__ void k_grid_alloc(CellGrids2 g);
@@ -102,6 +50,22 @@ inline void grid_build(const CellGrids2& g, hipStream_t s) {
   if (M > 0) k_grid_insert<<<dim3((M + 1023) / 1024, g.P, 2), 256, 0, s>>>(g);  // kInsChunk
   k_grid_alloc<<<dim3((T + 4095) / 4096, g.P, 2), 256, 0, s>>>(g);                // 256 * kAllocPer
   if (M > 0) k_grid_scatter<<<dim3((M + 255) / 256, g.P, 2), 256, 0, s>>>(g);
+}
+
+// The same four kernels for one grid of P problems (z extent 1: only g[0] is read). The second entry
+// of the argument is a copy of the first, so no launch ever carries a pointer that is not a live
+// allocation of the caller's.
+inline void grid_build_one(const CellGrid& one, int P, hipStream_t s) {
+  CellGrids2 g;
+  g.g[0] = one;
+  g.g[1] = one;
+  g.P = P;
+  const int T = 1 << one.log2T;
+  const int M = one.cap;
+  k_grid_clear<<<dim3((T + 255) / 256, P, 1), 256, 0, s>>>(g);
+  if (M > 0) k_grid_insert<<<dim3((M + 1023) / 1024, P, 1), 256, 0, s>>>(g);  // kInsChunk
+  k_grid_alloc<<<dim3((T + 4095) / 4096, P, 1), 256, 0, s>>>(g);                // 256 * kAllocPer
+  if (M > 0) k_grid_scatter<<<dim3((M + 255) / 256, P, 1), 256, 0, s>>>(g);
 }
 
 }  // namespace llsr

@@ -411,6 +411,40 @@ __global__ __launch_bounds__(256) void k_global_assemble(const GmChunk* ch, cons
   }
 }
 
+// performLoopClosure's source filter (MO:990-994): the points with (int)intensity >= 0, in order. The
+// conversion is x86-64's cvttss2si: NaN and values outside int's range become INT_MIN and drop,
+// values in (-1, 0) truncate to 0 and stay. One block walks the cloud in tiles of kLcBlock: a ballot
+// scan inside each wave, the wave totals through LDS, the running base in a register.
+constexpr int kLcBlock = 1024;
+__device__ __forceinline__ bool loop_keeps(float intensity) { return intensity > -1.0f && intensity < 2147483648.0f; }
+
+__global__ __launch_bounds__(kLcBlock) void k_loop_compact(const float4* in, int n, float4* out, int* n_out) {
+  constexpr int kWaves = kLcBlock / 64;
+  __shared__ int wtot[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, w = (tid >> 6) & (kWaves - 1);
+  int base = 0;
+  for (int t0 = 0; t0 < n; t0 += kLcBlock) {
+    const int i = t0 + tid;
+    float4 q = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    if (i < n) q = in[i];
+    const bool keep = i < n && loop_keeps(q.w);
+    const unsigned long long mk = __ballot(keep);
+    if (lane == 0) wtot[w] = __popcll(mk);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) {
+      const int c = wtot[k];
+      before += k < w ? c : 0;
+      total += c;
+    }
+    if (keep) out[base + before + __popcll(mk & ((1ull << lane) - 1ull))] = q;
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) *n_out = base;
+}
+
 template <class T>
 hipError_t grow(T*& p, size_t& cap, size_t need) {
   if (need <= cap) return hipSuccess;
@@ -475,6 +509,12 @@ struct llsr_map {
   // publishGlobalMap's call-to-call state: successful llsr_map_global calls since create / reset
   // (the reference's re-pointed globalMapKeyPosesDS / globalMapKeyFramesDS, MO:807, 836)
   int gm_calls = 0;
+  // loop closure (llsr_map_loop_submaps / llsr_map_loop_closure): the filtered source cloud, its
+  // count, and the map's own ICP workspace (created on first use)
+  float4* loopbuf = nullptr;
+  size_t cap_loop = 0;
+  int* loopcnt = nullptr;
+  llsr_icp* icp = nullptr;
 };
 
 static int32_t mfail(llsr_map* m, int32_t code, const std::string& msg) {
@@ -704,9 +744,10 @@ extern "C" void llsr_map_destroy(llsr_map* m) {
   (void)hipSetDevice(m->device);
   (void)hipStreamSynchronize(m->stream);
   void* dev[] = {m->store, m->key, m->key2, m->val, m->val2, m->flag, m->rank, m->tmp, m->mm, m->par, m->dtab,
-                 m->mapbuf, m->dsbuf, m->poses, m->dxf, m->isbuf};
+                 m->mapbuf, m->dsbuf, m->poses, m->dxf, m->isbuf, m->loopbuf, m->loopcnt};
   for (void* p : dev)
     if (p) (void)hipFree(p);
+  if (m->icp) llsr_icp_destroy(m->icp);
   if (m->htab) (void)hipHostFree(m->htab);
   if (m->hstage) (void)hipHostFree(m->hstage);
   if (m->hcnt) (void)hipHostFree(m->hcnt);
@@ -1247,5 +1288,164 @@ extern "C" int32_t llsr_map_set_key_poses(llsr_map* m, const float* poses6, int3
   // MO:1759-1761: the queue of transformed recent keyframes goes; latestFrameID stays. The store
   // keeps keyframes in their own frames, so nothing else was transformed with the old poses.
   m->sel.ids.clear();
+  return LLSR_OK;
+}
+
+// ---- loop closure: the submaps of detectLoopClosure (MO:894-981) and performLoopClosure (MO:983-1094) ----
+namespace {
+
+struct LoopClouds {        // where one call's clouds lie in the map's scratch
+  const float4* source = nullptr;     // filtered latest keyframe (loopbuf)
+  const float4* target = nullptr;     // the history submap (mapbuf, after the raw source)
+  const float4* source_ds = nullptr;  // dsbuf
+  const float4* target_ds = nullptr;
+};
+
+// §16 "Candidate and submaps" steps 1-5 in the map's scratch; the sizes go to rep, the places to lc.
+// Changes no map state. rep->found = 0: nothing else was touched.
+int32_t loop_submaps_scratch(llsr_map* m, const llsr_loop_config* cfg, const float* robot_pos, double now,
+                             llsr_loop_report* rep, LoopClouds* lc, hipStream_t s) {
+  const int K = (int)m->kf.size();
+  if (K == 0) return LLSR_OK;  // MO:985
+  std::vector<float> p4(4 * (size_t)K);
+  std::vector<double> times((size_t)K);
+  for (int k = 0; k < K; ++k) {
+    for (int a = 0; a < 3; ++a) p4[4 * (size_t)k + a] = m->kf[k].pose[a];
+    p4[4 * (size_t)k + 3] = (float)k;
+    times[k] = m->kf[k].time;
+  }
+  const int closest = llsr_loop_candidate(p4.data(), times.data(), K, robot_pos, now, cfg->search_radius, cfg->min_time_gap);
+  if (closest < -1) return mfail(m, LLSR_EINVAL, "loop closure: the candidate search failed");
+  if (closest < 0) return LLSR_OK;
+  // one descriptor table: the latest keyframe, then the history window; corner then surf each
+  std::vector<int> list = {K - 1};
+  for (int j = -cfg->search_num; j <= cfg->search_num; ++j)
+    if (closest + j >= 0 && closest + j < K) list.push_back(closest + j);
+  std::vector<GmKf> kfs(list.size());
+  long long tot = 0, n_raw = 0;
+  for (size_t i = 0; i < list.size(); ++i) {
+    const llsr_map::Kf& k = m->kf[list[i]];
+    GmKf& g = kfs[i];
+    std::memcpy(g.t, k.pose, sizeof g.t);
+    g.pad = 0;
+    for (int a = 0; a < 3; ++a) {
+      g.n[a] = k.n[a];
+      g.src[a] = k.off[a];
+      g.dst1[a] = g.dst2[a] = -1;
+      if (a < 2) {
+        g.dst2[a] = tot;
+        tot += k.n[a];
+      }
+    }
+    if (i == 0) n_raw = tot;
+  }
+  const long long n_target = tot - n_raw;
+  if (tot >= (long long)INT32_MAX)
+    return mfail(m, LLSR_ERANGE, "loop closure: more than LLSR_VOXEL_GRID_MAX_POINTS points in the submaps");
+  // every buffer of the call is sized before any of it is used
+  MAP_OK(m, hipStreamSynchronize(s));
+  MAP_OK(m, grow(m->mapbuf, m->cap_map, (size_t)std::max(tot, 1ll)));
+  MAP_OK(m, grow(m->loopbuf, m->cap_loop, (size_t)std::max(n_raw, 1ll)));
+  MAP_OK(m, grow(m->dsbuf, m->cap_ds, (size_t)std::max(tot, 1ll)));
+  if (!m->loopcnt) MAP_OK(m, hipMalloc((void**)&m->loopcnt, sizeof(int)));
+  if (!m->hcnt) MAP_OK(m, hipHostMalloc((void**)&m->hcnt, 4 * sizeof(int)));
+  int32_t rc = gm_assemble(m, kfs, nullptr, nullptr, m->mapbuf, s);
+  if (rc != LLSR_OK) return rc;
+  k_loop_compact<<<1, kLcBlock, 0, s>>>(m->mapbuf, (int)n_raw, m->loopbuf, m->loopcnt);
+  MAP_OK(m, hipGetLastError());
+  MAP_OK(m, hipMemcpyAsync(m->hcnt, m->loopcnt, sizeof(int), hipMemcpyDeviceToHost, s));
+  MAP_OK(m, hipStreamSynchronize(s));
+  const long long n_source = m->hcnt[0];
+  if (n_source < 0 || n_source > n_raw) return mfail(m, LLSR_EIO, "loop closure: bad source count");
+  const std::vector<VgCloud> two = {{m->loopbuf, n_source, cfg->leaf}, {m->mapbuf + n_raw, n_target, cfg->leaf}};
+  long long off[3];
+  rc = vg_run(m, two, m->dsbuf, off, s);
+  if (rc != LLSR_OK) return rc;
+  rep->found = 1;
+  rep->closest_id = closest;
+  rep->latest_id = K - 1;
+  rep->n_source = n_source;
+  rep->n_target = n_target;
+  rep->n_source_ds = off[1] - off[0];
+  rep->n_target_ds = off[2] - off[1];
+  lc->source = m->loopbuf;
+  lc->target = m->mapbuf + n_raw;
+  lc->source_ds = m->dsbuf + off[0];
+  lc->target_ds = m->dsbuf + off[1];
+  return LLSR_OK;
+}
+
+int32_t loop_copy_out(llsr_map* m, const float4* from, int64_t n, float* to, hipStream_t s) {
+  if (to && n > 0) MAP_OK(m, hipMemcpyAsync(to, from, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+  return LLSR_OK;
+}
+
+void loop_report_clear(llsr_loop_report* rep) {
+  std::memset(rep, 0, sizeof *rep);
+  rep->closest_id = rep->latest_id = -1;
+}
+
+}  // namespace
+
+extern "C" int32_t llsr_map_loop_submaps(llsr_map* m, const llsr_loop_config* cfg, const float robot_pos[3], double now,
+                                         llsr_loop_report* rep, float* d_source, int64_t cap_source, float* d_target,
+                                         int64_t cap_target, float* d_source_ds, int64_t cap_sds, float* d_target_ds,
+                                         int64_t cap_tds, void* hip_stream) {
+  if (!m || !cfg || !robot_pos || !rep || cfg->search_num < 0 || !(cfg->leaf > 0) || bad_out(d_source, cap_source) ||
+      bad_out(d_target, cap_target) || bad_out(d_source_ds, cap_sds) || bad_out(d_target_ds, cap_tds))
+    return mfail(m, LLSR_EINVAL, "loop submaps: bad arguments (a NULL output takes capacity 0)");
+  const auto t0 = std::chrono::steady_clock::now();
+  loop_report_clear(rep);
+  MAP_OK(m, hipSetDevice(m->device));
+  const hipStream_t s = pick(m, hip_stream);
+  LoopClouds lc;
+  int32_t rc = loop_submaps_scratch(m, cfg, robot_pos, now, rep, &lc, s);
+  if (rc != LLSR_OK || !rep->found) return rc;
+  if ((d_source && cap_source < rep->n_source) || (d_target && cap_target < rep->n_target) ||
+      (d_source_ds && cap_sds < rep->n_source_ds) || (d_target_ds && cap_tds < rep->n_target_ds))
+    return mfail(m, LLSR_ERANGE, "loop submaps: a cloud exceeds its output capacity");
+  if ((rc = loop_copy_out(m, lc.source, rep->n_source, d_source, s)) != LLSR_OK) return rc;
+  if ((rc = loop_copy_out(m, lc.target, rep->n_target, d_target, s)) != LLSR_OK) return rc;
+  if ((rc = loop_copy_out(m, lc.source_ds, rep->n_source_ds, d_source_ds, s)) != LLSR_OK) return rc;
+  if ((rc = loop_copy_out(m, lc.target_ds, rep->n_target_ds, d_target_ds, s)) != LLSR_OK) return rc;
+  MAP_OK(m, hipStreamSynchronize(s));
+  rep->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_map_loop_closure(llsr_map* m, llsr_icp* w, const llsr_loop_config* cfg, const float robot_pos[3],
+                                         double now, llsr_loop_report* rep, float* d_aligned, int64_t cap_aligned,
+                                         float* d_target_ds, int64_t cap_tds, void* hip_stream) {
+  if (!m || !cfg || !robot_pos || !rep || cfg->search_num < 0 || !(cfg->leaf > 0) || bad_out(d_aligned, cap_aligned) ||
+      bad_out(d_target_ds, cap_tds))
+    return mfail(m, LLSR_EINVAL, "loop closure: bad arguments (a NULL output takes capacity 0)");
+  const auto t0 = std::chrono::steady_clock::now();
+  loop_report_clear(rep);
+  MAP_OK(m, hipSetDevice(m->device));
+  const hipStream_t s = pick(m, hip_stream);
+  LoopClouds lc;
+  int32_t rc = loop_submaps_scratch(m, cfg, robot_pos, now, rep, &lc, s);
+  if (rc != LLSR_OK || !rep->found) return rc;
+  if ((d_aligned && cap_aligned < rep->n_source) || (d_target_ds && cap_tds < rep->n_target_ds))
+    return mfail(m, LLSR_ERANGE, "loop closure: a cloud exceeds its output capacity");
+  if (rep->n_source > LLSR_ICP_MAX_POINTS || rep->n_target > LLSR_ICP_MAX_POINTS)
+    return mfail(m, LLSR_ERANGE, "loop closure: more than LLSR_ICP_MAX_POINTS points to align");
+  if (!w) {
+    if (!m->icp) m->icp = llsr_icp_create(m->device);
+    if (!m->icp) return mfail(m, LLSR_ENOMEM, "loop closure: no ICP workspace");
+    w = m->icp;
+  }
+  // MO:1011-1012: the raw clouds, not the downsampled ones
+  rc = llsr_icp_align(w, reinterpret_cast<const float*>(lc.source), (int32_t)rep->n_source,
+                      reinterpret_cast<const float*>(lc.target), (int32_t)rep->n_target, cfg, &rep->icp, d_aligned, s);
+  if (rc != LLSR_OK) return mfail(m, rc, std::string("loop closure: ") + llsr_icp_last_error(w));
+  if ((rc = loop_copy_out(m, lc.target_ds, rep->n_target_ds, d_target_ds, s)) != LLSR_OK) return rc;
+  // MO:1038-1040
+  rep->accepted = rep->icp.converged && !(rep->icp.fitness > (double)cfg->fitness_score);
+  if (rep->accepted)
+    llsr_loop_constraint(rep->icp.T, m->kf[rep->latest_id].pose, m->kf[rep->closest_id].pose, rep->icp.fitness,
+                         rep->pose_from, rep->pose_to, &rep->variance);
+  MAP_OK(m, hipStreamSynchronize(s));
+  rep->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return LLSR_OK;
 }

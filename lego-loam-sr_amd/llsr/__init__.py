@@ -50,6 +50,8 @@ EXPORTS = [
     "llsr_mapping_global_map", "llsr_mapping_save_map", "llsr_row_bins",
     "llsr_loop_config_lidar", "llsr_map_set_keyframe_time", "llsr_map_keyframe_times",
     "llsr_map_set_key_poses", "llsr_loop_candidate", "llsr_umeyama3", "llsr_loop_constraint",
+    "llsr_icp_align_host", "llsr_icp_create", "llsr_icp_destroy", "llsr_icp_last_error", "llsr_icp_align",
+    "llsr_icp_last_times", "llsr_map_loop_submaps", "llsr_map_loop_closure",
 ]
 
 
@@ -160,6 +162,17 @@ def lib():
         L.llsr_umeyama3.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.llsr_loop_constraint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                            C.c_void_p]
+        L.llsr_icp_align_host.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(_abi.LoopConfig),
+                                          C.POINTER(_abi.IcpResult), C.c_void_p]
+        L.llsr_icp_create.argtypes = [C.c_int32]
+        L.llsr_icp_destroy.argtypes = [C.c_void_p]
+        L.llsr_icp_last_error.argtypes = [C.c_void_p]
+        L.llsr_icp_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(_abi.LoopConfig),
+                                     C.POINTER(_abi.IcpResult), C.c_void_p, C.c_void_p]
+        L.llsr_icp_last_times.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 3
+        _loop = [C.POINTER(_abi.LoopConfig), C.c_void_p, C.c_double, C.POINTER(_abi.LoopReport)]
+        L.llsr_map_loop_submaps.argtypes = [C.c_void_p] + _loop + [C.c_void_p, C.c_int64] * 4 + [C.c_void_p]
+        L.llsr_map_loop_closure.argtypes = [C.c_void_p, C.c_void_p] + _loop + [C.c_void_p, C.c_int64] * 2 + [C.c_void_p]
         L.llsr_mapping_init.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.MapConfig)]
         L.llsr_mapping_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.llsr_mapping_fetch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.MappingSlot)]
@@ -175,12 +188,16 @@ def lib():
                                       C.c_void_p, C.c_void_p]
         for fn in EXPORTS:
             if fn not in ("llsr_last_error", "llsr_kernel_name", "llsr_destroy", "llsr_map_create",
-                          "llsr_map_destroy", "llsr_map_last_error", "llsr_build_id"):
+                          "llsr_map_destroy", "llsr_map_last_error", "llsr_build_id", "llsr_icp_create",
+                          "llsr_icp_destroy", "llsr_icp_last_error"):
                 getattr(L, fn).restype = C.c_int32
         L.llsr_destroy.restype = None
         L.llsr_map_create.restype = C.c_void_p
         L.llsr_map_destroy.restype = None
         L.llsr_map_last_error.restype = C.c_char_p
+        L.llsr_icp_create.restype = C.c_void_p
+        L.llsr_icp_destroy.restype = None
+        L.llsr_icp_last_error.restype = C.c_char_p
         _LIB = L
     return _LIB
 
@@ -792,6 +809,71 @@ def loop_constraint(T, pose_latest, pose_closest, fitness: float):
     return pf, pt, var.value
 
 
+def icp_align_host(src, tgt, cfg: _abi.LoopConfig | None = None) -> dict:
+    """The loop closure's ICP (llsr_icp_align_host, host only, serial) of the (n, 4)
+    clouds src onto tgt: the llsr_icp_result fields and "aligned", the source moved by T."""
+    a = np.ascontiguousarray(src, np.float32).reshape(-1, 4)
+    b = np.ascontiguousarray(tgt, np.float32).reshape(-1, 4)
+    cfg = cfg or loop_config()
+    res = _abi.IcpResult()
+    out = np.zeros((max(len(a), 1), 4), np.float32)
+    rc = lib().llsr_icp_align_host(a.ctypes.data, len(a), b.ctypes.data, len(b), C.byref(cfg), C.byref(res),
+                                   out.ctypes.data)
+    if rc != 0:
+        raise LlsrError(f"llsr_icp_align_host: {rc}")
+    r = res.as_dict()
+    r["aligned"] = out[:len(a)]
+    return r
+
+
+class Icp:
+    """The loop closure's ICP on a HIP device (llsr_icp, include/llsr.h): a workspace that owns the
+    target's cell grid and the loop's buffers. Clouds are torch CUDA float32 tensors of shape (n, 4)."""
+
+    def __init__(self, device: int = 0):
+        import torch
+        self._torch = torch
+        self.device = torch.device("cuda", device)
+        self._w = lib().llsr_icp_create(device)
+        if not self._w:
+            raise LlsrError("llsr_icp_create failed: no HIP device")
+        self._s = torch.cuda.Stream(device=self.device)
+
+    def close(self):
+        if getattr(self, "_w", None):
+            lib().llsr_icp_destroy(self._w)
+            self._w = None
+
+    def __del__(self):
+        self.close()
+
+    def align(self, src, tgt, cfg: _abi.LoopConfig | None = None) -> dict:
+        """llsr_icp_align of src onto tgt: the llsr_icp_result fields and "aligned" (a device tensor)."""
+        torch = self._torch
+        src, tgt = (np.array(c, np.float32) if isinstance(c, np.ndarray) else c for c in (src, tgt))
+        a = torch.as_tensor(src, dtype=torch.float32, device=self.device).reshape(-1, 4).contiguous()
+        b = torch.as_tensor(tgt, dtype=torch.float32, device=self.device).reshape(-1, 4).contiguous()
+        out = torch.empty((max(a.shape[0], 1), 4), dtype=torch.float32, device=self.device)
+        cfg = cfg or loop_config()
+        res = _abi.IcpResult()
+        self._s.wait_stream(torch.cuda.current_stream(self.device))
+        rc = lib().llsr_icp_align(self._w, C.c_void_p(a.data_ptr() if a.shape[0] else 0), a.shape[0],
+                                  C.c_void_p(b.data_ptr() if b.shape[0] else 0), b.shape[0], C.byref(cfg),
+                                  C.byref(res), C.c_void_p(out.data_ptr()), C.c_void_p(self._s.cuda_stream))
+        if rc != 0:
+            raise LlsrError(f"llsr_icp_align failed ({rc}): {lib().llsr_icp_last_error(self._w).decode()}")
+        torch.cuda.current_stream(self.device).wait_stream(self._s)
+        r = res.as_dict()
+        r["aligned"] = out[:a.shape[0]]
+        return r
+
+    def last_times(self) -> dict:
+        """HIP-event ms of the last align: the correspondence and solve kernels summed, the whole call."""
+        c, v, t = C.c_float(), C.c_float(), C.c_float()
+        lib().llsr_icp_last_times(self._w, C.byref(c), C.byref(v), C.byref(t))
+        return {"corr_ms": c.value, "solve_ms": v.value, "total_ms": t.value}
+
+
 def _global_map(torch, device, call, caps, edge: bool, planar: bool) -> dict:
     """Run a llsr_map_global-shaped call with output buffers of caps[global, edge, planar] points,
     growing them once to the reported sizes on LLSR_ERANGE."""
@@ -966,6 +1048,56 @@ class LocalMap:
         self._check(rc, "llsr_map_save")
         self._leave()
         return c, su
+
+    def _loop_call(self, call, names, sizes, caps):
+        """Run a loop-closure call with one output buffer per name, growing them once to the reported
+        sizes on LLSR_ERANGE; caps (points per output) may force the first attempt's capacities."""
+        torch = self._torch
+        rep = _abi.LoopReport()
+        caps = list(caps) if caps is not None else [1] * len(names)
+        for _ in range(2):
+            bufs = [torch.empty((max(c, 1), 4), dtype=torch.float32, device=self.device) for c in caps]
+            args = []
+            for b in bufs:
+                args += [C.c_void_p(b.data_ptr()), b.shape[0]]
+            rc = call(rep, *args)
+            if rc != _abi.LLSR_ERANGE:
+                break
+            caps = [max(c, int(getattr(rep, f))) for c, f in zip(caps, sizes)]
+        r = rep.as_dict()
+        r["rc"] = rc
+        for nm, f, b in zip(names, sizes, bufs):
+            r[nm] = b[:int(getattr(rep, f))] if rc == 0 and rep.found else None
+        return r
+
+    def loop_submaps(self, robot_pos, now: float, cfg: _abi.LoopConfig | None = None, caps=None) -> dict:
+        """detectLoopClosure's candidate and submaps (MO:894-981, llsr_map_loop_submaps): the report
+        fields and the "source", "target", "source_ds", "target_ds" clouds (None without a candidate)."""
+        pos = np.ascontiguousarray(robot_pos, np.float32)
+        cfg = cfg or loop_config()
+        s = self._enter()
+        call = lambda rep, *out: lib().llsr_map_loop_submaps(self._m, C.byref(cfg), pos.ctypes.data, now,  # noqa: E731
+                                                            C.byref(rep), *out, s)
+        r = self._loop_call(call, ("source", "target", "source_ds", "target_ds"),
+                            ("n_source", "n_target", "n_source_ds", "n_target_ds"), caps)
+        self._check(r.pop("rc"), "llsr_map_loop_submaps")
+        self._leave()
+        return r
+
+    def loop_closure(self, robot_pos, now: float, cfg: _abi.LoopConfig | None = None, icp: "Icp | None" = None,
+                     caps=None) -> dict:
+        """performLoopClosure up to the pose constraint (MO:983-1081, llsr_map_loop_closure): the report
+        fields (the alignment's among them) and the "aligned" and "target_ds" clouds."""
+        pos = np.ascontiguousarray(robot_pos, np.float32)
+        cfg = cfg or loop_config()
+        s = self._enter()
+        w = icp._w if icp is not None else None
+        call = lambda rep, *out: lib().llsr_map_loop_closure(self._m, w, C.byref(cfg), pos.ctypes.data, now,  # noqa: E731
+                                                            C.byref(rep), *out, s)
+        r = self._loop_call(call, ("aligned", "target_ds"), ("n_source", "n_target_ds"), caps)
+        self._check(r.pop("rc"), "llsr_map_loop_closure")
+        self._leave()
+        return r
 
     def set_keyframe_time(self, index: int, seconds: float):
         """cloudKeyPoses6D[index].time (llsr_map_set_keyframe_time); unset times never match a loop."""

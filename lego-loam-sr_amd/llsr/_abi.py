@@ -301,6 +301,38 @@ class LoopConfig(C.Structure):
                 ("icp_max_correspondence_distance", C.c_double)]
 
 
+ICP_STATES = ("none", "iterations", "transform", "abs_mse", "rel_mse", "no_correspondences")
+
+
+class IcpResult(C.Structure):
+    """llsr_icp_result (include/llsr.h): one finished alignment."""
+    _fields_ = [("converged", C.c_int32), ("state", C.c_int32), ("iterations", C.c_int32),
+                ("n_pairs_last", C.c_int32), ("fitness", C.c_double), ("T", C.c_float * 16)]
+
+    def as_dict(self) -> dict:
+        return {"converged": bool(self.converged), "state": int(self.state), "iterations": int(self.iterations),
+                "n_pairs_last": int(self.n_pairs_last), "fitness": float(self.fitness),
+                "T": np.array(self.T[:], dtype=np.float32).reshape(4, 4)}
+
+
+class LoopReport(C.Structure):
+    """llsr_loop_report (include/llsr.h): one detectLoopClosure + performLoopClosure."""
+    _fields_ = [("found", C.c_int32), ("closest_id", C.c_int32), ("latest_id", C.c_int32), ("accepted", C.c_int32),
+                ("n_source", C.c_int64), ("n_target", C.c_int64), ("n_source_ds", C.c_int64),
+                ("n_target_ds", C.c_int64), ("icp", IcpResult), ("pose_from", C.c_float * 6),
+                ("pose_to", C.c_float * 6), ("variance", C.c_float), ("ms", C.c_float)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k in ("found", "closest_id", "latest_id", "accepted", "n_source",
+                                                 "n_target", "n_source_ds", "n_target_ds")}
+        d.update(self.icp.as_dict())
+        d["pose_from"] = np.array(self.pose_from[:], dtype=np.float32)
+        d["pose_to"] = np.array(self.pose_to[:], dtype=np.float32)
+        d["variance"] = np.float32(self.variance)
+        d["ms"] = float(self.ms)
+        return d
+
+
 class MappingSlot(C.Structure):
     """llsr_mapping_slot (include/llsr.h): one sequence's MapOptimization state after the last call."""
     _fields_ = [("frames", C.c_int32), ("mo_frames", C.c_int32), ("keyframes", C.c_int32), ("lm_ran", C.c_int32),
