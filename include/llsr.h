@@ -845,6 +845,98 @@ int32_t llsr_odometry_fetch_lm(llsr_handle* h, int32_t b, float transform_lm[6])
 int32_t llsr_mapping_batch_odom(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
                                 const llsr_odom_sample* samples, const uint8_t* overwrite, void* hip_stream);
 
+/* ---- /imu_type and adjustDistortion's IMU de-skew (featureAssociation.cpp:315-351, 452-563, 600-690, 788) ----
+ * Once one /imu_type message has arrived (imuPointerLast >= 0; use_imu_undistortion is not read on
+ * this path) adjustDistortion interpolates the IMU queue at every segmented point's time and rotates
+ * the point into the scan-start frame. The queue lives on the host side of the library (no device, no
+ * handle), like /odom2 above; a scan takes a linear window of it, and the feature stage de-skews on
+ * the device from that window (llsr_stage_imu) or on the host (llsr_imu_deskew_host); both run the
+ * same per-point body (csrc/llsr_imu.h). DESIGN.md §17. */
+#define LLSR_IMU_QUEUE 200
+#define LLSR_IMU_WINDOW_MAX (LLSR_IMU_QUEUE + 1)
+typedef struct llsr_imu_msg {  /* the sensor_msgs/Imu fields imuHandler reads */
+  int32_t sec;                 /* header.stamp */
+  uint32_t nanosec;
+  double orientation[4];       /* x, y, z, w */
+  double angular_velocity[3];
+  double linear_acceleration[3];
+} llsr_imu_msg;
+typedef struct llsr_imu_state {  /* FeatureAssociation's IMU queue members (featureAssociation.h:68-119) */
+  int32_t pointer_last;            /* imuPointerLast: -1 until the first message */
+  int32_t pointer_last_iteration;  /* imuPointerLastIteration */
+  double time[LLSR_IMU_QUEUE];
+  float roll[LLSR_IMU_QUEUE], pitch[LLSR_IMU_QUEUE], yaw[LLSR_IMU_QUEUE];
+  float acc[3][LLSR_IMU_QUEUE];               /* imuAccX / Y / Z */
+  float velo[3][LLSR_IMU_QUEUE];              /* imuVeloX / Y / Z */
+  float shift[3][LLSR_IMU_QUEUE];             /* imuShiftX / Y / Z */
+  float angular_velo[3][LLSR_IMU_QUEUE];      /* imuAngularVeloX / Y / Z */
+  float angular_rotation[3][LLSR_IMU_QUEUE];  /* imuAngularRotationX / Y / Z */
+} llsr_imu_state;
+/* The constructor's values (FA:237-239, 261-270): zeros, pointer_last = -1. */
+int32_t llsr_imu_init(llsr_imu_state* st);
+/* imuHandler + AccumulateIMUShiftAndRotation (FA:315-351, 452-489): tf2 getRPY of the orientation in
+ * double; the gravity-compensated acceleration from double sin / cos, narrowed to float; the ring
+ * advances; the accumulate step rotates the acceleration with float sin / cos and, when the gap to the
+ * entry before is below scan_period, writes shift / velocity / angular rotation (each update in
+ * double, narrowed on the store). A gap >= scan_period leaves those nine entries as the ring held
+ * them 200 messages earlier (or zero). */
+int32_t llsr_imu_callback(llsr_imu_state* st, const llsr_imu_msg* msg, float scan_period);
+typedef struct llsr_imu_sample {  /* one ring entry as the de-skew reads it */
+  double time;
+  float roll, pitch, yaw;
+  float velo[3], shift[3], angular_rotation[3];
+} llsr_imu_sample;
+/* The ring entries one adjustDistortion call can read, in walk order, then FA:788
+ * (pointer_last_iteration = pointer_last). *n = 0 when no message ever arrived (pointer_last < 0: no
+ * de-skew; pointer_last_iteration becomes -1 as in the reference, whose next walk would then start
+ * outside the array: here -1 is read as entry 0, the first message); otherwise *n = ((pointer_last - pointer_last_iteration) mod 200) + 1
+ * candidates and out[k], k = 0 .. *n, is ring entry (pointer_last_iteration - 1 + k) mod 200 copied as
+ * it stands: out[0] is the "back" of the first candidate, the search walks k = 1 .. *n and stops at
+ * k = *n (= pointer_last) at the latest. The ring walk starts at pointer_last_iteration and steps
+ * (front + 1) mod 200 until it meets pointer_last, so it visits exactly these entries in this order,
+ * also across the wrap, and every "back" (front + 199) mod 200 it reads is out[k - 1]. With no new
+ * message since the previous scan, or exactly 200 of them, the pointers are equal: the walk does not
+ * advance and *n = 1 (one candidate); that is not "no IMU", which only pointer_last < 0 means. */
+int32_t llsr_imu_scan_window(llsr_imu_state* st, llsr_imu_sample out[LLSR_IMU_WINDOW_MAX], int32_t* n);
+typedef struct llsr_imu_report {   /* FeatureAssociation's members after adjustDistortion */
+  float start[3];                  /* imuRollStart, imuPitchStart, imuYawStart */
+  float angular_from_start[3];     /* imuAngularFromStartX / Y / Z */
+  float cur[3];                    /* imuRollCur, imuPitchCur, imuYawCur of the last point */
+  float velo_from_start[3];        /* imuVeloFromStartX / Y / ZCur of the last point */
+} llsr_imu_report;
+typedef struct llsr_imu_carry {    /* what one scan hands to the next; zeros before the first */
+  float angular_rotation_last[3];  /* imuAngularRotationX / Y / ZLast */
+  llsr_imu_report report;          /* members a scan does not write keep their value */
+} llsr_imu_carry;
+/* adjustDistortion (FA:565-690) of one scan on the host, serially. scan_time_*: the segmented cloud's
+ * header stamp (timeScanCur); window / n: llsr_imu_scan_window's (n = 0: no IMU, the plain LOAM swap);
+ * seg_xyzi: S segmented points (IP frame, intensity = ring + col / 1e4); orientation: segInfo's
+ * start_orientation, end_orientation, orientation_diff; carry: updated in place; loam_xyzi_out: S
+ * points; report (may be NULL): carry->report after the scan. Point 0 latches the start state and is
+ * not rotated; a scan that writes no member (n = 0, S = 0; S = 1 for velo_from_start) reports the
+ * carried one. */
+int32_t llsr_imu_deskew_host(const llsr_config* cfg, int32_t scan_time_sec, uint32_t scan_time_nanosec,
+                             const llsr_imu_sample* window, int32_t n, const float* seg_xyzi, int32_t S,
+                             const float orientation[3], llsr_imu_carry* carry, float* loam_xyzi_out,
+                             llsr_imu_report* report);
+/* Arm the next batch call of this handle (llsr_process_scan / llsr_process_batch, llsr_odometry_batch /
+ * _batch_odom, llsr_mapping_batch / _batch_odom) with the slots' windows: host arrays scan_sec[B],
+ * scan_nanosec[B], offsets[B + 1] and the packed samples; slot b's window is
+ * samples[offsets[b] .. offsets[b + 1]) = llsr_imu_scan_window's out[0 .. n] (n + 1 entries), or empty
+ * for a slot without IMU (plain path, carry untouched). The arrays are copied to handle-owned pinned
+ * memory here and uploaded asynchronously on that batch's stream. The batch must have the same B
+ * (else it returns LLSR_EINVAL and the staging stays). The staging is consumed when the call's
+ * feature stage has been enqueued; a call that fails before that leaves it staged. A failure later in
+ * the call (the LM or MapOptimization part) finds the carry advanced together with the odometry, as
+ * the mapping batch's rollback contract states for the odometry, and the staging consumed. Waits for
+ * the handle's previous batch (it may still read the pinned arrays). Each slot carries its
+ * llsr_imu_carry on the device, zeroed by llsr_reset_state, llsr_odometry_reset and
+ * llsr_mapping_reset. */
+int32_t llsr_stage_imu(llsr_handle* h, const int32_t* scan_sec, const uint32_t* scan_nanosec,
+                       const llsr_imu_sample* samples, const int64_t* offsets, int32_t B);
+/* Slot b's report (its carried members) after the last batch; synchronises with it. */
+int32_t llsr_fetch_imu_report(llsr_handle* h, int32_t b, llsr_imu_report* report);
+
 /* ---- Input wire formats (llsr_input.hip) ----
  * sensor_msgs/PointCloud2 (PointField datatype codes, sensor_msgs/msg/PointField.msg) decoded as
  * pcl::fromROSMsg<PointXYZI> (IP:196): x, y, z, intensity are taken from the fields of that name

@@ -213,6 +213,60 @@ class Handle {
   llsr_handle* h_ = nullptr;
 };
 
+// FeatureAssociation's IMU queue (FA:237-239, 261-270) behind a mutex. Thread layout: on_message is
+// imuHandler (FA:315-351, 452-489) and runs on the /imu_type subscription's thread; window() is taken
+// once per scan by Projection::run on the projection thread, where this library runs the feature
+// stage (adjustDistortion included) right after the segmentation. The reference reads the queue
+// unsynchronised from runFeatureAssociation's thread while the handler writes it, so which messages
+// a scan sees there depends on timing; here a scan sees the snapshot taken under the mutex at
+// window(): every message whose callback returned before it, none after (and FA:788 happens in the
+// same critical section). on_message accepts any message type with sensor_msgs/Imu's header.stamp,
+// orientation, angular_velocity and linear_acceleration fields.
+class ImuInput {
+ public:
+  struct Window {
+    llsr_imu_sample samples[LLSR_IMU_WINDOW_MAX];
+    int32_t n = 0;  // candidates; 0: no /imu_type message yet
+  };
+  explicit ImuInput(float scan_period) : scan_period_(scan_period) {
+    check(llsr_imu_init(&st_), nullptr, "llsr_imu_init");
+  }
+  template <class Msg>
+  void on_message(const Msg& msg) {
+    llsr_imu_msg m = llsr_imu_msg();
+    m.sec = msg.header.stamp.sec;
+    m.nanosec = msg.header.stamp.nanosec;
+    m.orientation[0] = msg.orientation.x;
+    m.orientation[1] = msg.orientation.y;
+    m.orientation[2] = msg.orientation.z;
+    m.orientation[3] = msg.orientation.w;
+    m.angular_velocity[0] = msg.angular_velocity.x;
+    m.angular_velocity[1] = msg.angular_velocity.y;
+    m.angular_velocity[2] = msg.angular_velocity.z;
+    m.linear_acceleration[0] = msg.linear_acceleration.x;
+    m.linear_acceleration[1] = msg.linear_acceleration.y;
+    m.linear_acceleration[2] = msg.linear_acceleration.z;
+    std::lock_guard<std::mutex> lk(m_);
+    check(llsr_imu_callback(&st_, &m, scan_period_), nullptr, "llsr_imu_callback");
+    ++messages_;
+  }
+  // the entries the scan that starts now can read; advances imuPointerLastIteration (FA:788)
+  void window(Window& w) {
+    std::lock_guard<std::mutex> lk(m_);
+    check(llsr_imu_scan_window(&st_, w.samples, &w.n), nullptr, "llsr_imu_scan_window");
+  }
+  int64_t messages() const {
+    std::lock_guard<std::mutex> lk(m_);
+    return messages_;
+  }
+
+ private:
+  mutable std::mutex m_;
+  llsr_imu_state st_;
+  float scan_period_;
+  int64_t messages_ = 0;
+};
+
 // One handle and its host output buffers (capacity H*W per array, llsr_query_sizes), for the
 // single-scan call shape the nodes use; one per pipeline thread, as the reference runs one thread
 // per node.
@@ -282,6 +336,22 @@ class Projection {
     check(llsr_process_scan(h_, xyzi_.data(), (int32_t)(xyzi_.size() / 4), &o_), h_, "llsr_process_scan");
   }
 
+  // ... with the IMU de-skew of adjustDistortion (FA:600-690): stamp = the cloud's header stamp
+  // (timeScanCur, FA:2761); takes the scan's window from `imu` here, on this thread
+  template <class Cloud>
+  void run(const Cloud& laser_cloud_in, int32_t stamp_sec, uint32_t stamp_nanosec, ImuInput& imu) {
+    imu.window(imu_window_);
+    const int64_t off[2] = {0, imu_window_.n > 0 ? imu_window_.n + 1 : 0};
+    check(llsr_stage_imu(h_, &stamp_sec, &stamp_nanosec, imu_window_.samples, off, 1), h_, "llsr_stage_imu");
+    run(laser_cloud_in);
+  }
+  // FeatureAssociation's IMU members after the last scan
+  llsr_imu_report imu_report() const {
+    llsr_imu_report r;
+    check(llsr_fetch_imu_report(h_, 0, &r), h_, "llsr_fetch_imu_report");
+    return r;
+  }
+
   // the marshalling below, on this handle's last scan
   template <class CloudInfo>
   void cloud_info(CloudInfo& msg) const { llsr_ros2::cloud_info(o_, rings_, msg); }
@@ -310,6 +380,7 @@ class Projection {
   size_t cells_ = 0;
   llsr_scan_out o_ = llsr_scan_out();
   std::vector<float> xyzi_, seg_, loam_, lflat_, out_, rng_, sint_, oint_, shadow_;
+  ImuInput::Window imu_window_;
   std::vector<int32_t> start_, end_, edge_, sharp_, flat_;
   std::vector<uint8_t> gflag_;
   std::vector<uint32_t> col_;

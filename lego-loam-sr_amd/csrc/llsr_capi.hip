@@ -26,6 +26,7 @@ __global__ void k_ground_elev_ransac(DevCfg, DevBufs);
 template <bool kLds> __global__ void k_label(DevCfg, DevBufs);
 __global__ void k_segment(DevCfg, const float4*, const int64_t*, DevBufs);
 void launch_fa_points(const DevCfg&, const DevBufs&, int, hipStream_t);
+void launch_fa_points_imu(const DevCfg&, const DevBufs&, const ImuDev&, int, hipStream_t);
 __global__ void k_select_ring(DevCfg, DevBufs);
 __global__ void k_vox_top(DevCfg, DevBufs, VoxRanges);
 __global__ void k_vox_leaf(DevCfg, DevBufs, VoxRanges);
@@ -347,7 +348,67 @@ extern "C" int32_t llsr_reset_state(llsr_handle* h) {
   HIP_OK(h, hipMemsetAsync(h->d.clabel, 0, n, h->stream));
   HIP_OK(h, hipMemsetAsync(h->d.phantom, 0, sizeof(int) * (size_t)h->max_batch, h->stream));
   HIP_OK(h, hipMemsetD32Async(h->d.seg_zero, h->dc.HW, (size_t)h->max_batch, h->stream));
+  if (h->imu.d_carry)  // the IMU members carried from scan to scan (FA:255-257)
+    HIP_OK(h, hipMemsetAsync(h->imu.d_carry, 0, sizeof(llsr_imu_carry) * (size_t)h->max_batch, h->stream));
   HIP_OK(h, hipStreamSynchronize(h->stream));
+  return LLSR_OK;
+}
+
+// ---- IMU de-skew staging (include/llsr.h; the kernel side is k_fa_points_imu, llsr_fa.hip) ----
+static int32_t imu_alloc(llsr_handle* h) {
+  auto& m = h->imu;
+  if (m.dev) return LLSR_OK;
+  llsr_handle::Imu n;
+  const size_t B = (size_t)h->max_batch;
+  if (llsr_host::alloc_pool(n.dev, 0, [&](llsr_host::Carver& cv) {
+        llsr_host::imu_layout(cv, n, B, LLSR_IMU_WINDOW_MAX);
+      }) != hipSuccess ||
+      llsr_host::alloc_pool(n.host, 0, [&](llsr_host::Carver& cv) {
+        llsr_host::imu_host_layout(cv, n, B, LLSR_IMU_WINDOW_MAX);
+      }) != hipSuccess)
+    return fail(h, LLSR_ENOMEM, "IMU staging");
+  HIP_OK(h, hipMemset(n.d_carry, 0, sizeof(llsr_imu_carry) * B));
+  m = std::move(n);
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_stage_imu(llsr_handle* h, const int32_t* scan_sec, const uint32_t* scan_nanosec,
+                                  const llsr_imu_sample* samples, const int64_t* offsets, int32_t B) {
+  if (!h) return LLSR_EINVAL;
+  if (!scan_sec || !scan_nanosec || !offsets) return fail(h, LLSR_EINVAL, "llsr_stage_imu: null argument");
+  if (B < 1 || B > h->max_batch) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
+  if (offsets[0] != 0) return fail(h, LLSR_EINVAL, "llsr_stage_imu: offsets[0] != 0");
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = offsets[b + 1] - offsets[b];  // none, or the back entry + 1 .. 200 candidates
+    if (n != 0 && (n < 2 || n > LLSR_IMU_WINDOW_MAX)) return fail(h, LLSR_EINVAL, "llsr_stage_imu: window length");
+  }
+  if (offsets[B] > 0 && !samples) return fail(h, LLSR_EINVAL, "llsr_stage_imu: samples is NULL");
+  HIP_OK(h, hipSetDevice(h->device));
+  const int32_t rc = imu_alloc(h);
+  if (rc != LLSR_OK) return rc;
+  // the pinned arrays may still feed the previous batch's upload
+  const int32_t rs = sync_last(h);
+  if (rs != LLSR_OK) return rs;
+  auto& m = h->imu;
+  for (int b = 0; b <= B; ++b) m.h_off[b] = (int)offsets[b];
+  for (int b = 0; b < B; ++b) m.h_time[b] = scan_sec[b] + scan_nanosec[b] / 1e9;  // FA:2761
+  if (offsets[B] > 0) std::memcpy(m.h_samples, samples, sizeof(llsr_imu_sample) * (size_t)offsets[B]);
+  m.B = B;
+  m.any = offsets[B] > 0;
+  m.armed = true;
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_fetch_imu_report(llsr_handle* h, int32_t b, llsr_imu_report* report) {
+  if (!h || !report) return fail(h, LLSR_EINVAL, "null argument");
+  if (b < 0 || b >= h->max_batch) return fail(h, LLSR_ERANGE, "slot index outside the handle's slots");
+  *report = llsr_imu_report{};
+  if (!h->imu.d_carry) return LLSR_OK;  // never staged: the constructor's zeros
+  const int32_t rc = sync_last(h);
+  if (rc != LLSR_OK) return rc;
+  llsr_imu_carry c;
+  HIP_OK(h, hipMemcpy(&c, h->imu.d_carry + b, sizeof c, hipMemcpyDeviceToHost));
+  *report = c.report;
   return LLSR_OK;
 }
 
@@ -383,6 +444,7 @@ extern "C" int32_t llsr_process_batch(llsr_handle* h, const float* d_xyzi, const
                                       int32_t B, void* hip_stream) {
   if (!h || !d_xyzi || !d_offsets) return fail(h, LLSR_EINVAL, "null argument");
   if (B < 1 || B > h->max_batch) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
+  if (h->imu.armed && h->imu.B != B) return fail(h, LLSR_EINVAL, "llsr_stage_imu staged another batch size");
   hipStream_t s;
   HIP_OK(h, enter(h, hip_stream, &s));
   // the slot buffers and the FA carry-over state are shared by every batch of this handle: a
@@ -437,7 +499,16 @@ extern "C" int32_t llsr_process_batch(llsr_handle* h, const float* d_xyzi, const
   mark();
   k_segment<<<B, per_scan_threads(c), 0, s>>>(c, pts, d_offsets, h->d);
   mark();
-  launch_fa_points(c, h->d, B, s);
+  if (h->imu.armed && h->imu.any) {  // staged windows: uploaded on this stream, ahead of their reader
+    auto& m = h->imu;
+    HIP_OK(h, hipMemcpyAsync(m.d_samples, m.h_samples, sizeof(llsr_imu_sample) * (size_t)m.h_off[B],
+                             hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(m.d_off, m.h_off, sizeof(int) * (size_t)(B + 1), hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(m.d_time, m.h_time, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, s));
+    launch_fa_points_imu(c, h->d, ImuDev{m.d_samples, m.d_off, m.d_time, m.d_carry}, B, s);
+  } else {
+    launch_fa_points(c, h->d, B, s);
+  }
   mark();
   k_select_ring<<<dim3(c.H, B), 256, 0, s>>>(c, h->d);
   mark();
@@ -457,6 +528,7 @@ extern "C" int32_t llsr_process_batch(llsr_handle* h, const float* d_xyzi, const
     h->ring_head = (h->ring_head + 1) % llsr_handle::kRing;
     h->ring_used += 1;
   }
+  h->imu.armed = false;  // consumed: the slots' carry advanced with this feature stage
   h->last_stream = s;
   h->last_B = B;
   h->last_pts = pts;

@@ -7,6 +7,7 @@
 #include "../../include/llsr.h"
 #include "llsr_mapping.h"
 #include "llsr_odo.h"
+#include "llsr_imu.h"
 #include "llsr_odom_guess.h"
 
 extern "C" int32_t llsr_mapping_associate(const float* ts_fa, const float* bef, const float* aft, float* ts,
@@ -131,5 +132,41 @@ extern "C" int32_t llsr_update_initial_guess(const llsr_odom_sample* sample, con
   float ts[6];
   for (int k = 0; k < 6; ++k) ts[k] = transform_sum[k];  // transform_cur may alias transform_sum
   llsr_odom::update_initial_guess(*sample, ts, transform_cur);
+  return LLSR_OK;
+}
+
+// ---- /imu_type and adjustDistortion's IMU de-skew (FA:315-351, 452-563, 600-690, 788): llsr_imu.h
+extern "C" int32_t llsr_imu_init(llsr_imu_state* st) {
+  if (!st) return LLSR_EINVAL;
+  llsr_imu::init(*st);
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_imu_callback(llsr_imu_state* st, const llsr_imu_msg* msg, float scan_period) {
+  if (!st || !msg || st->pointer_last < -1 || st->pointer_last >= LLSR_IMU_QUEUE) return LLSR_EINVAL;
+  double roll, pitch, yaw;
+  llsr_mapping::tf2_get_rpy(msg->orientation, roll, pitch, yaw);  // tf2::convert copies x, y, z, w
+  llsr_imu::callback_rpy(*st, *msg, roll, pitch, yaw, scan_period);
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_imu_scan_window(llsr_imu_state* st, llsr_imu_sample* out, int32_t* n) {
+  if (!st || !out || !n || st->pointer_last < -1 || st->pointer_last >= LLSR_IMU_QUEUE ||
+      st->pointer_last_iteration < -1 || st->pointer_last_iteration >= LLSR_IMU_QUEUE)
+    return LLSR_EINVAL;
+  *n = llsr_imu::scan_window(*st, out);
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_imu_deskew_host(const llsr_config* cfg, int32_t scan_time_sec, uint32_t scan_time_nanosec,
+                                        const llsr_imu_sample* window, int32_t n, const float* seg_xyzi, int32_t S,
+                                        const float* orientation, llsr_imu_carry* carry, float* loam_xyzi_out,
+                                        llsr_imu_report* report) {
+  if (!cfg || !orientation || !carry || n < 0 || n > LLSR_IMU_QUEUE || (n > 0 && !window) || S < 0 ||
+      (S > 0 && (!seg_xyzi || !loam_xyzi_out)))
+    return LLSR_EINVAL;
+  const double scan_time = scan_time_sec + scan_time_nanosec / 1e9;  // FA:2761
+  llsr_imu::deskew_host(cfg->scan_period, scan_time, window, n, seg_xyzi, S, orientation, carry, loam_xyzi_out);
+  if (report) *report = carry->report;
   return LLSR_OK;
 }

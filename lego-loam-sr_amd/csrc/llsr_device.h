@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/llsr.h"
 #include "llsr_libm.h"
 
 namespace llsr {
@@ -93,6 +94,15 @@ struct DevBufs {
   int* phantom;         // [B] FA carry-over state: cloudSmoothness[4].ind (value is always 0)
   int* seg_zero;        // [B] seg_ground / seg_col / seg_range are zero on [seg_zero, HW) (k_segment's
                         // last S; HW after llsr_reset_state), so a batch clears only [S, seg_zero)
+};
+
+// A staged batch's IMU windows (llsr_stage_imu) as k_fa_points_imu reads them, and the slots' carry.
+// Slot b's window is samples[off[b] .. off[b + 1]): n + 1 entries (llsr_imu_scan_window), or none.
+struct ImuDev {
+  const llsr_imu_sample* samples;
+  const int* off;           // [B + 1]
+  const double* scan_time;  // [B] timeScanCur
+  llsr_imu_carry* carry;    // [max_batch]
 };
 
 // The work items of the PCL-order VoxelGrid's sort (k_vox_top -> k_vox_leaf), owned by the handle:

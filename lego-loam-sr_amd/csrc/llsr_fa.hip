@@ -6,6 +6,7 @@
 #include <climits>
 
 #include "llsr_device.h"
+#include "llsr_imu.h"
 #include "llsr_isort.h"
 #include "llsr_libm.h"
 
@@ -28,9 +29,9 @@ constexpr int kFaT = 256;
 constexpr int kFaTile = 4 * kFaT - 12;  // 1012 points: with the +-5 point halo and the +-6 flag halo, 4 slots per lane
 
 // LOAM-frame point of segmented point i (FA:565-598): orientation branch by the halfPassed latch
-// (`first`), relative time, intensity = ring + scan_period * relTime.
-__device__ __forceinline__ float4 loam_point(const DevCfg& c, float4 p, int i, int first, float start, float endo,
-                                             float diff) {
+// (`first`), relative time (also to *rel), intensity = ring + scan_period * relTime.
+__device__ __forceinline__ float4 loam_point_rel(const DevCfg& c, float4 p, int i, int first, float start, float endo,
+                                                 float diff, float* rel) {
   float o = -atan2f_(p.y, p.x);  // point.x = y, point.z = x (FA:573-577)
   if (i <= first) {
     o = ori_branch1(o, start);
@@ -41,10 +42,25 @@ __device__ __forceinline__ float4 loam_point(const DevCfg& c, float4 p, int i, i
   }
   const float relTime = (o - start) / diff;
   const float inten = (float)(int)(p.w) + c.scan_period * relTime;
+  *rel = relTime;
   return make_float4(p.y, p.z, p.x, inten);
 }
+__device__ __forceinline__ float4 loam_point(const DevCfg& c, float4 p, int i, int first, float start, float endo,
+                                             float diff) {
+  float rel;
+  return loam_point_rel(c, p, i, first, start, endo, diff, &rel);
+}
 
-__global__ __launch_bounds__(kFaT) void k_fa_points(DevCfg c, DevBufs d) {
+// The kernel body. kImu (k_fa_points_imu, launched only when a batch has a staged window): a slot
+// with a window (uniform over the workgroup) de-skews every point of the tile and of its +-5 halo
+// (FA:600-690, llsr_imu.h) before it goes into tp[] / loam[], so the curvature sees de-skewed
+// neighbours across tile boundaries. The window's times and angles sit in LDS (at most 201 x 20 B);
+// point 0's start state is recomputed by every workgroup; the velocity / angular-rotation entries
+// are read from global memory by the lanes that own point 0 and point S - 1, which write the slot's
+// report and carry (distinct members, one workgroup each: no race). A slot without a window takes
+// the plain path and leaves its carry alone.
+template <bool kImu>
+__device__ __forceinline__ void fa_points_body(const DevCfg& c, const DevBufs& d, const ImuDev* im) {
   constexpr int kTile = kFaTile;
   __shared__ float4 tp[kTile + 10];
   __shared__ uint8_t fl[kTile + 12];  // bit0 A_i, bit1 B_i, bit2 C_i for i in [t0-6, t0+T+6)
@@ -82,6 +98,43 @@ __global__ __launch_bounds__(kFaT) void k_fa_points(DevCfg c, DevBufs d) {
     }
   }
 
+  [[maybe_unused]] bool imu = false;  // uniform over the workgroup
+  [[maybe_unused]] llsr_imu::Window win{nullptr, nullptr, nullptr, nullptr, 0};
+  [[maybe_unused]] llsr_imu::Start st0{};
+  [[maybe_unused]] const llsr_imu_sample* wsmp = nullptr;
+  [[maybe_unused]] double scan_time = 0.0;
+  if constexpr (kImu) {
+    __shared__ double w_t[LLSR_IMU_WINDOW_MAX];
+    __shared__ float w_r[LLSR_IMU_WINDOW_MAX], w_p[LLSR_IMU_WINDOW_MAX], w_y[LLSR_IMU_WINDOW_MAX];
+    __shared__ llsr_imu::Start s_st;
+    const int o0 = im->off[b], nw = im->off[b + 1] - o0;  // entries: candidates + 1
+    imu = nw >= 2 && nw <= LLSR_IMU_WINDOW_MAX;
+    if (imu) {
+      wsmp = im->samples + o0;
+      scan_time = im->scan_time[b];
+      for (int k = tid; k < nw; k += nt) {
+        const llsr_imu_sample e = wsmp[k];
+        w_t[k] = e.time;
+        w_r[k] = e.roll;
+        w_p[k] = e.pitch;
+        w_y[k] = e.yaw;
+      }
+      win = llsr_imu::Window{w_t, w_r, w_p, w_y, nw - 1};
+      __syncthreads();
+      if (tid == 0) {  // point 0: never rotated, latches the start state (FA:649-685)
+        float rel, cur[3];
+        float4 p0 = loam_point_rel(c, seg[0], 0, first, start, endo, diff, &rel);
+        llsr_imu::Sel sel;
+        llsr_imu::Start stl{};
+        llsr_imu::deskew_point(win, scan_time, c.scan_period, rel, true, stl, cur, &sel, &p0.x, &p0.y, &p0.z);
+        llsr_imu::latch_start(cur, sel, &stl);
+        s_st = stl;
+        if (t0 == 0) llsr_imu::first_point_members(stl, wsmp, &im->carry[b]);
+      }
+      __syncthreads();
+      st0 = s_st;
+    }
+  }
   const float* rng = d.seg_range + base;
   const uint32_t* col = d.seg_col + base;
   uint8_t* picked = d.picked + base;
@@ -115,7 +168,20 @@ __global__ __launch_bounds__(kFaT) void k_fa_points(DevCfg c, DevBufs d) {
     const int q = tid + u * nt, k = t0 - 5 + q;
     if (q >= kTile + 10) continue;
     if (k >= 0 && k < S) {
-      const float4 lp = loam_point(c, pp[u], k, first, start, endo, diff);
+      float4 lp;
+      if constexpr (kImu) {
+        float rel;
+        lp = loam_point_rel(c, pp[u], k, first, start, endo, diff, &rel);
+        if (imu) {
+          float cur[3];
+          llsr_imu::Sel sel;
+          llsr_imu::deskew_point(win, scan_time, c.scan_period, rel, k == 0, st0, cur, &sel, &lp.x, &lp.y, &lp.z);
+          if (k == S - 1 && q >= 5 && q < kTile + 5)  // the lane that owns the last point
+            llsr_imu::last_point_members(st0, sel, cur, k == 0, wsmp, &im->carry[b].report);
+        }
+      } else {
+        lp = loam_point(c, pp[u], k, first, start, endo, diff);
+      }
       tp[q] = lp;
       if (q >= 5 && q < kTile + 5) loam[k] = lp;
     } else {
@@ -180,8 +246,17 @@ __global__ __launch_bounds__(kFaT) void k_fa_points(DevCfg c, DevBufs d) {
   }
 }
 
+__global__ __launch_bounds__(kFaT) void k_fa_points(DevCfg c, DevBufs d) { fa_points_body<false>(c, d, nullptr); }
+__global__ __launch_bounds__(kFaT) void k_fa_points_imu(DevCfg c, DevBufs d, ImuDev im) {
+  fa_points_body<true>(c, d, &im);
+}
+
 void launch_fa_points(const DevCfg& c, const DevBufs& d, int B, hipStream_t s) {
   k_fa_points<<<dim3((c.HW + kFaTile - 1) / kFaTile, B), kFaT, 0, s>>>(c, d);
+}
+// a batch with at least one staged IMU window
+void launch_fa_points_imu(const DevCfg& c, const DevBufs& d, const ImuDev& im, int B, hipStream_t s) {
+  k_fa_points_imu<<<dim3((c.HW + kFaTile - 1) / kFaTile, B), kFaT, 0, s>>>(c, d, im);
 }
 
 // ---------------------------------------------------------------------------------------------

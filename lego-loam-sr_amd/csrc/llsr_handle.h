@@ -164,6 +164,22 @@ struct LLSR_HIDDEN llsr_handle {
     GrowBuf outl, ds, tot, cmap;       // cmap: empty-map base
     MapSmall sm;
   } mp;
+  // IMU de-skew (llsr_stage_imu): device windows + per-slot carry and their pinned staging, allocated
+  // on the first staging call; `armed` until a batch's feature stage consumes it
+  struct Imu {
+    llsr_host::DevMem dev;
+    llsr_host::PinnedMem host;
+    llsr_imu_sample* d_samples = nullptr;  // packed windows of the batch
+    int* d_off = nullptr;                  // [max_batch + 1]
+    double* d_time = nullptr;              // [max_batch] timeScanCur
+    llsr_imu_carry* d_carry = nullptr;     // [max_batch]
+    llsr_imu_sample* h_samples = nullptr;
+    int* h_off = nullptr;
+    double* h_time = nullptr;
+    bool armed = false;
+    bool any = false;  // at least one slot of the staged batch has a window
+    int B = 0;
+  } imu;
   std::string err;
 };
 

@@ -54,6 +54,22 @@ void feature_layout(Carver& c, D& d, size_t B, size_t H, size_t HW, size_t cnt, 
   c.take(d.seg_zero, B);
 }
 
+// The staged IMU windows (llsr_stage_imu): B slots of at most `win` samples, and the slots' carry;
+// ... and the pinned host staging behind them.
+template <class I>
+void imu_layout(Carver& c, I& m, size_t B, size_t win) {
+  c.take(m.d_samples, B * win);
+  c.take(m.d_off, B + 1);
+  c.take(m.d_time, B);
+  c.take(m.d_carry, B);
+}
+template <class I>
+void imu_host_layout(Carver& c, I& m, size_t B, size_t win) {
+  c.take(m.h_samples, B * win);
+  c.take(m.h_off, B + 1);
+  c.take(m.h_time, B);
+}
+
 // The two cell grids (CellGrids2) of P problems: cap_[k] points and 1 << log2T[k] slots each.
 template <class G>
 void grids_layout(Carver& c, G& g, size_t P, const int cap[2], const int log2T[2]) {

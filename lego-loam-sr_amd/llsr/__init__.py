@@ -52,6 +52,8 @@ EXPORTS = [
     "llsr_map_set_key_poses", "llsr_loop_candidate", "llsr_umeyama3", "llsr_loop_constraint",
     "llsr_icp_align_host", "llsr_icp_create", "llsr_icp_destroy", "llsr_icp_last_error", "llsr_icp_align",
     "llsr_icp_last_times", "llsr_map_loop_submaps", "llsr_map_loop_closure",
+    "llsr_imu_init", "llsr_imu_callback", "llsr_imu_scan_window", "llsr_imu_deskew_host", "llsr_stage_imu",
+    "llsr_fetch_imu_report",
 ]
 
 
@@ -131,6 +133,14 @@ def lib():
         L.llsr_odom_init.argtypes = [C.POINTER(_abi.OdomState)]
         L.llsr_odom_callback.argtypes = [C.POINTER(_abi.OdomState), C.POINTER(_abi.OdometryMsg)]
         L.llsr_update_initial_guess.argtypes = [C.POINTER(_abi.OdomSample), C.c_void_p, C.c_void_p]
+        L.llsr_imu_init.argtypes = [C.POINTER(_abi.ImuStateStruct)]
+        L.llsr_imu_callback.argtypes = [C.POINTER(_abi.ImuStateStruct), C.POINTER(_abi.ImuMsg), C.c_float]
+        L.llsr_imu_scan_window.argtypes = [C.POINTER(_abi.ImuStateStruct), C.c_void_p, C.POINTER(C.c_int32)]
+        L.llsr_imu_deskew_host.argtypes = [C.POINTER(Config), C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p, C.POINTER(_abi.ImuCarry), C.c_void_p,
+                                           C.POINTER(_abi.ImuReport)]
+        L.llsr_stage_imu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.llsr_fetch_imu_report.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.ImuReport)]
         L.llsr_map_config_default.argtypes = [C.POINTER(_abi.MapConfig)]
         L.llsr_map_config_lidar.argtypes = [C.POINTER(_abi.MapConfig), C.c_int32]
         L.llsr_map_create.argtypes = [C.POINTER(_abi.MapConfig), C.c_int32]
@@ -264,6 +274,28 @@ class Pipeline:
     def fetch(self, b: int) -> dict:
         self._check(lib().llsr_fetch_scan(self._h, b, C.byref(self.out.struct)), "llsr_fetch_scan")
         return self.out.result()
+
+    def stage_imu(self, scan_stamps, windows):
+        """llsr_stage_imu: arm this handle's next batch call with the slots' IMU windows. scan_stamps:
+        B (sec, nanosec) pairs of the segmented clouds' headers; windows: B entries, each None / empty
+        (slot without IMU) or ImuState.scan_window()'s structured array (n + 1 samples)."""
+        B = len(scan_stamps)
+        sec = np.array([s[0] for s in scan_stamps], np.int32)
+        nsec = np.array([s[1] for s in scan_stamps], np.uint32)
+        ws = [np.zeros(0, IMU_SAMPLE_DTYPE) if w is None else np.ascontiguousarray(w, IMU_SAMPLE_DTYPE) for w in windows]
+        if len(ws) != B:
+            raise ValueError("one window per scan stamp")
+        off = np.zeros(B + 1, np.int64)
+        off[1:] = np.cumsum([len(w) for w in ws])
+        samples = np.concatenate(ws) if B else np.zeros(0, IMU_SAMPLE_DTYPE)
+        self._check(lib().llsr_stage_imu(self._h, sec.ctypes.data, nsec.ctypes.data, samples.ctypes.data,
+                                         off.ctypes.data, B), "llsr_stage_imu")
+
+    def fetch_imu_report(self, b: int) -> dict:
+        """llsr_fetch_imu_report: slot b's IMU members after the last batch, {field: float32 [3]}."""
+        r = _abi.ImuReport()
+        self._check(lib().llsr_fetch_imu_report(self._h, b, C.byref(r)), "llsr_fetch_imu_report")
+        return imu_report_dict(r)
 
     def fetch_vis_clouds(self, b: int) -> dict:
         """publishClouds' visualization clouds of slot b (llsr_fetch_vis_clouds): {name: float32 [n, 4]}."""
@@ -596,6 +628,72 @@ class TransformFusion:
         """transformSum, transformIncre, transformMapped, transformBefMapped, transformAftMapped."""
         st = self.state
         return np.concatenate([np.array(getattr(st, f), np.float32) for f, _ in st._fields_])
+
+
+IMU_SAMPLE_DTYPE = np.dtype([("time", np.float64), ("roll", np.float32), ("pitch", np.float32), ("yaw", np.float32),
+                             ("velo", np.float32, 3), ("shift", np.float32, 3),
+                             ("angular_rotation", np.float32, 3)])
+assert IMU_SAMPLE_DTYPE.itemsize == C.sizeof(_abi.ImuSample)
+
+
+def imu_report_dict(r: "_abi.ImuReport") -> dict:
+    return {f: np.array(getattr(r, f), np.float32) for f, _ in _abi.ImuReport._fields_}
+
+
+class ImuState:
+    """FeatureAssociation's IMU queue (llsr_imu_state): feed every /imu_type message to callback(),
+    take scan_window() once per scan, where adjustDistortion would run."""
+
+    def __init__(self, scan_period: float = 0.1):
+        self.scan_period = float(scan_period)
+        self.state = _abi.ImuStateStruct()
+        rc = lib().llsr_imu_init(C.byref(self.state))
+        if rc != 0:
+            raise LlsrError(f"llsr_imu_init: {rc}")
+
+    def callback(self, sec: int, nanosec: int, orientation, angular_velocity, linear_acceleration):
+        """imuHandler + AccumulateIMUShiftAndRotation (FA:315-351, 452-489) of one message."""
+        m = _abi.ImuMsg(int(sec), int(nanosec), (C.c_double * 4)(*map(float, orientation)),
+                        (C.c_double * 3)(*map(float, angular_velocity)),
+                        (C.c_double * 3)(*map(float, linear_acceleration)))
+        rc = lib().llsr_imu_callback(C.byref(self.state), C.byref(m), self.scan_period)
+        if rc != 0:
+            raise LlsrError(f"llsr_imu_callback: {rc}")
+
+    def scan_window(self) -> np.ndarray:
+        """llsr_imu_scan_window: the n + 1 ring entries this scan's de-skew can read (empty: no IMU
+        yet), as IMU_SAMPLE_DTYPE records; then imuPointerLastIteration = imuPointerLast (FA:788)."""
+        out = np.zeros(_abi.IMU_WINDOW_MAX, IMU_SAMPLE_DTYPE)
+        n = C.c_int32(0)
+        rc = lib().llsr_imu_scan_window(C.byref(self.state), out.ctypes.data, C.byref(n))
+        if rc != 0:
+            raise LlsrError(f"llsr_imu_scan_window: {rc}")
+        return out[: n.value + 1].copy() if n.value > 0 else out[:0].copy()
+
+    def arrays(self) -> dict:
+        """Every ring array and both pointers (for comparisons)."""
+        st = self.state
+        d = {"pointer_last": int(st.pointer_last), "pointer_last_iteration": int(st.pointer_last_iteration)}
+        for f, _ in st._fields_[2:]:
+            d[f] = np.ctypeslib.as_array(getattr(st, f)).copy()
+        return d
+
+
+def imu_deskew_host(cfg, scan_stamp, window, seg_xyzi, orientation, carry: "_abi.ImuCarry"):
+    """llsr_imu_deskew_host: adjustDistortion (FA:565-690) of one scan on the host. Returns (loam_xyzi
+    float32 [S, 4], report dict); `carry` is updated in place."""
+    w = np.zeros(0, IMU_SAMPLE_DTYPE) if window is None else np.ascontiguousarray(window, IMU_SAMPLE_DTYPE)
+    n = max(len(w) - 1, 0)
+    seg = np.ascontiguousarray(seg_xyzi, np.float32).reshape(-1, 4)
+    ori = np.ascontiguousarray(orientation, np.float32).reshape(3)
+    out = np.zeros_like(seg)
+    rep = _abi.ImuReport()
+    rc = lib().llsr_imu_deskew_host(C.byref(cfg), int(scan_stamp[0]), int(scan_stamp[1]), w.ctypes.data, n,
+                                    seg.ctypes.data, seg.shape[0], ori.ctypes.data, C.byref(carry), out.ctypes.data,
+                                    C.byref(rep))
+    if rc != 0:
+        raise LlsrError(f"llsr_imu_deskew_host: {rc}")
+    return out, imu_report_dict(rep)
 
 
 def odom_init() -> "_abi.OdomState":

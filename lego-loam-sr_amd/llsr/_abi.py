@@ -252,6 +252,43 @@ class OdomState(C.Structure):
                 ("last", OdomSample)]
 
 
+IMU_QUEUE = 200
+IMU_WINDOW_MAX = IMU_QUEUE + 1
+
+
+class ImuMsg(C.Structure):
+    """llsr_imu_msg: the sensor_msgs/Imu fields imuHandler reads."""
+    _fields_ = [("sec", C.c_int32), ("nanosec", C.c_uint32), ("orientation", C.c_double * 4),
+                ("angular_velocity", C.c_double * 3), ("linear_acceleration", C.c_double * 3)]
+
+
+class ImuStateStruct(C.Structure):
+    """llsr_imu_state: FeatureAssociation's IMU queue members (featureAssociation.h:68-119)."""
+    _fields_ = [("pointer_last", C.c_int32), ("pointer_last_iteration", C.c_int32),
+                ("time", C.c_double * IMU_QUEUE),
+                ("roll", C.c_float * IMU_QUEUE), ("pitch", C.c_float * IMU_QUEUE), ("yaw", C.c_float * IMU_QUEUE),
+                ("acc", (C.c_float * IMU_QUEUE) * 3), ("velo", (C.c_float * IMU_QUEUE) * 3),
+                ("shift", (C.c_float * IMU_QUEUE) * 3), ("angular_velo", (C.c_float * IMU_QUEUE) * 3),
+                ("angular_rotation", (C.c_float * IMU_QUEUE) * 3)]
+
+
+class ImuSample(C.Structure):
+    """llsr_imu_sample: one ring entry as the de-skew reads it."""
+    _fields_ = [("time", C.c_double), ("roll", C.c_float), ("pitch", C.c_float), ("yaw", C.c_float),
+                ("velo", C.c_float * 3), ("shift", C.c_float * 3), ("angular_rotation", C.c_float * 3)]
+
+
+class ImuReport(C.Structure):
+    """llsr_imu_report: FeatureAssociation's members after adjustDistortion."""
+    _fields_ = [("start", C.c_float * 3), ("angular_from_start", C.c_float * 3), ("cur", C.c_float * 3),
+                ("velo_from_start", C.c_float * 3)]
+
+
+class ImuCarry(C.Structure):
+    """llsr_imu_carry: what one scan hands to the next."""
+    _fields_ = [("angular_rotation_last", C.c_float * 3), ("report", ImuReport)]
+
+
 class FusionState(C.Structure):
     """llsr_fusion_state: TransformFusion's members (transformFusion.h)."""
     _fields_ = [("transform_sum", C.c_float * 6), ("transform_incre", C.c_float * 6),

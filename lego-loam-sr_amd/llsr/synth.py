@@ -163,8 +163,12 @@ def sensor_attitude(seed: int) -> np.ndarray:
     pitch and a few cm in z, which is what the scan-to-scan surf step solves for (pitch, roll and
     the vertical translation, featureAssociation.cpp:2001-2003): without it that step converges
     at its first iteration."""
-    k = float(seed % 64)
-    ph = np.random.default_rng(7700001 + seed // 64).uniform(0.0, 2.0 * np.pi, (4, 2))
+    return _attitude_at(seed // 64, float(seed % 64))
+
+
+def _attitude_at(drive: int, k: float) -> np.ndarray:
+    """sensor_attitude's sinusoids of drive `drive` at the (fractional) frame index k."""
+    ph = np.random.default_rng(7700001 + drive).uniform(0.0, 2.0 * np.pi, (4, 2))
     amp = np.array([0.05, np.deg2rad(2.0), np.deg2rad(2.0), np.deg2rad(3.0)])
     freq = np.array([[0.9, 2.3], [0.7, 1.9], [0.8, 2.1], [0.4, 1.3]])
     return amp * (0.6 * np.sin(freq[:, 0] * k + ph[:, 0]) + 0.4 * np.sin(freq[:, 1] * k + ph[:, 1]))
@@ -238,6 +242,47 @@ def odom_message(seed: int) -> np.ndarray:
     out = np.zeros(13, np.float64)
     out[0:4] = q
     out[4:7] = (0.5 * (seed % 64), y, dz)
+    return out
+
+
+IMU_MSG_DTYPE = np.dtype([("sec", np.int32), ("nanosec", np.uint32), ("orientation", np.float64, 4),
+                          ("angular_velocity", np.float64, 3), ("linear_acceleration", np.float64, 3)])
+
+
+def scan_stamp(seed: int, t0_sec: int = 1000, scan_period: float = 0.1) -> tuple[int, int]:
+    """Header stamp (sec, nanosec) of frame `seed` of its drive: t0_sec + (seed % 64) scan periods."""
+    ns = int(round((seed % 64) * scan_period * 1e9))
+    return t0_sec + ns // 1_000_000_000, ns % 1_000_000_000
+
+
+def imu_stream(seed: int, rate_hz: float, frames: int, t0_sec: int = 1000, scan_period: float = 0.1,
+               lead: float = 0.05) -> np.ndarray:
+    """The /imu_type messages (sensor_msgs/Imu, IMU_MSG_DTYPE records in stamp order) of a drive from
+    `lead` seconds before frame `seed` starts (scan_stamp) to the end of frame seed + frames - 1, at
+    rate_hz. The orientation is `sensor_attitude`'s attitude, its sinusoids evaluated at the message's
+    fractional frame index, as the quaternion of _rot_zyx(roll, pitch, yaw); the angular velocity is
+    the attitude's central difference over 1 ms; the acceleration is gravity in the body frame plus
+    the second difference of dz, in the axis order imuHandler expects. Deterministic."""
+    drive, k0 = seed // 64, seed % 64
+    dt_ns = int(round(1e9 / rate_hz))
+    start_ns = int(round((k0 * scan_period - lead) * 1e9))
+    end_ns = int(round((k0 + frames) * scan_period * 1e9))
+    stamps = np.arange(start_ns, end_ns, dt_ns, dtype=np.int64)
+    out = np.zeros(len(stamps), IMU_MSG_DTYPE)
+    h = 1e-3 / scan_period
+    for i, ns in enumerate(stamps):
+        k = ns * 1e-9 / scan_period
+        dz, roll, pitch, yaw = _attitude_at(drive, k)
+        a0, a1 = _attitude_at(drive, k - h), _attitude_at(drive, k + h)
+        m = _rot_zyx(roll, pitch, yaw)
+        w = 0.5 * np.sqrt(1.0 + m[0, 0] + m[1, 1] + m[2, 2])
+        q = ((m[2, 1] - m[1, 2]) / (4.0 * w), (m[0, 2] - m[2, 0]) / (4.0 * w), (m[1, 0] - m[0, 1]) / (4.0 * w), w)
+        tot = t0_sec * 1_000_000_000 + int(ns)
+        out[i]["sec"], out[i]["nanosec"] = tot // 1_000_000_000, tot % 1_000_000_000
+        out[i]["orientation"] = q
+        out[i]["angular_velocity"] = (a1[1:] - a0[1:]) / 2e-3
+        az = (a1[0] - 2.0 * dz + a0[0]) / 1e-6
+        out[i]["linear_acceleration"] = m.T @ np.array([0.0, 0.0, 9.81 + az])
     return out
 
 
