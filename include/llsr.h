@@ -937,6 +937,39 @@ int32_t llsr_stage_imu(llsr_handle* h, const int32_t* scan_sec, const uint32_t* 
 /* Slot b's report (its carried members) after the last batch; synchronises with it. */
 int32_t llsr_fetch_imu_report(llsr_handle* h, int32_t b, llsr_imu_report* report);
 
+/* ---- use_imu_undistortion == true (featureAssociation.cpp:1456-1483, 1492-1550, 2329-2332,
+ * 2339-2349, 2557-2560, 2662-2663, 2786-2788) ----
+ * The switch of the reference's YAML (false in its three shipped blocks). on != 0: from the next
+ * batch call on, every odometry of this handle (llsr_odometry_batch / _batch_odom, llsr_mapping_batch /
+ * _batch_odom) runs the reference's branches under the switch; the default is off, and
+ * llsr_reset_state / llsr_odometry_reset / llsr_mapping_reset leave it as it is. Of a slot's
+ * llsr_imu_report after the scan's feature stage (llsr_fetch_imu_report) the branches read `start`
+ * (imuRoll / Pitch / YawStart) and `cur` (imuRoll / Pitch / YawCur of the last point, which the pre-LM
+ * updateInitialGuess copies to imuRoll / Pitch / YawLast); angular_from_start and velo_from_start are
+ * not read (their uses at FA:2351-2361 are commented out), and imuShiftFromStartX / Y / Z is always 0
+ * (ShiftToStartIMU is never called). A slot that was never staged reads the constructor's zeros. Per
+ * scan of a slot:
+ *   first scan: checkSystemInitialization adds imuPitchStart to transformSum[0] and imuRollStart to
+ *     transformSum[2] (FA:2329-2332);
+ *   later scans: under llsr_odometry_batch_odom / llsr_mapping_batch_odom, for a slot with
+ *     overwrite[b] != 0, the LM starts from llsr_update_initial_guess(samples[b], transformSum) instead
+ *     of the carried transformCur (the updateInitialGuess before updateTransformation, FA:2786-2788;
+ *     llsr_odometry_fetch_lm still returns the LM's own result); elsewhere the LM starts from the carried
+ *     transformCur as with the switch off. integrateTransformation ends in PluginIMURotation
+ *     (FA:2557-2560) and TransformToEnd runs its IMU tail (FA:1456-1483) on the four clouds (the shadow
+ *     points appended to the surf last cloud stay raw).
+ * Same single host sync per batch. DESIGN.md §18. */
+int32_t llsr_set_imu_undistortion(llsr_handle* h, int32_t on);
+/* The host twins of llsr_integrate_transformation / llsr_transform_to_end with the switch on, for the
+ * FA node's thread (no device, no handle); they read report->start and report->cur only and are
+ * bit-identical to the device path. out_xyzi may equal in_xyzi. llsr_first_scan_imu is
+ * checkSystemInitialization's add on a slot's first scan. */
+int32_t llsr_integrate_transformation_imu(float transform_sum[6], const float transform_cur[6],
+                                          const llsr_imu_report* report);
+int32_t llsr_transform_to_end_imu(const float transform_cur[6], const llsr_imu_report* report, const float* in_xyzi,
+                                  int32_t n, float* out_xyzi);
+int32_t llsr_first_scan_imu(float transform_sum[6], const llsr_imu_report* report);
+
 /* ---- Input wire formats (llsr_input.hip) ----
  * sensor_msgs/PointCloud2 (PointField datatype codes, sensor_msgs/msg/PointField.msg) decoded as
  * pcl::fromROSMsg<PointXYZI> (IP:196): x, y, z, intensity are taken from the fields of that name

@@ -13,6 +13,8 @@
 //                                               (on the FA thread, its own handle; step = solve + finish)
 //   FeatureAssociation::odomCallback         featureAssociation.cpp:354-383 -> OdomInput::on_message
 //   FeatureAssociation::updateInitialGuess   featureAssociation.cpp:2337-2402 -> OdomInput::apply
+//   use_imu_undistortion == true            featureAssociation.cpp:1456-1483, 2329-2332, 2557-2560,
+//                                            2786-2788 -> Odometry's constructor switch, FeatureClouds::imu
 //   FeatureAssociation::updateTransformation featureAssociation.cpp:2505-2535 -> update_transformation
 //   MapOptimization::scan2MapOptimization    mapOptmization.cpp:1572-1610 -> scan2map_optimization
 //   MapOptimization::publishGlobalMapThread  mapOptmization.cpp:305-315, 775-892 -> GlobalMap (opt-in)
@@ -157,6 +159,9 @@ struct FeatureClouds {
   Cloud corner_less_sharp;  // cornerPointsLessSharp
   Cloud surf_flat;          // surfPointsFlat + the shadow points (FA:1310-1314)
   Cloud surf_less_flat;     // surfPointsLessFlat (per-ring VoxelGrid)
+  // the scan's IMU members after adjustDistortion (Projection::imu_report; zeros without IMU): what
+  // Odometry reads when use_imu_undistortion is on
+  llsr_imu_report imu = llsr_imu_report();
 };
 
 // TransformToEnd (FA:1414-1490) of every point of `in` into `out` (may be the same cloud)
@@ -166,6 +171,16 @@ void transform_to_end(const float transform_cur[6], const Cloud& in, Cloud& out)
   repack_xyzi(in, a);
   const int32_t n = (int32_t)(a.size() / 4);
   check(llsr_transform_to_end(transform_cur, a.data(), n, a.data()), nullptr, "llsr_transform_to_end");
+  unpack_xyzi(a.data(), n, out);
+}
+
+// ... with use_imu_undistortion: the tail at FA:1456-1483 from the scan's IMU report
+template <class Cloud>
+void transform_to_end_imu(const float transform_cur[6], const llsr_imu_report& imu, const Cloud& in, Cloud& out) {
+  std::vector<float> a;
+  repack_xyzi(in, a);
+  const int32_t n = (int32_t)(a.size() / 4);
+  check(llsr_transform_to_end_imu(transform_cur, &imu, a.data(), n, a.data()), nullptr, "llsr_transform_to_end_imu");
   unpack_xyzi(a.data(), n, out);
 }
 
@@ -372,6 +387,7 @@ class Projection {
     projection_out(po, *po.segmented_cloud, *po.outlier_cloud);
     features(po.features.segmented, po.features.corner_sharp, po.features.corner_less_sharp, po.features.surf_flat,
              po.features.surf_less_flat);
+    po.features.imu = imu_report();
   }
 
  private:
@@ -415,14 +431,22 @@ llsr_s2s_report update_transformation(llsr_handle* h, const Cloud& corner_sharp,
 // transform_cur) for updateInitialGuess (FA:2790), then finish(f), then the node's publishOdometry;
 // step(f) = solve + finish leaves the LM's transformCur in place (LLSR_MODE_LM_APPLIED semantics).
 // Either way transform_cur carries over as the next LM's initial guess.
+// With use_imu_undistortion (the YAML switch, the constructor's argument) the order is
+// OdomInput::apply before solve(f) as well (the updateInitialGuess at FA:2786-2788: the LM starts
+// from the guess), solve(f), apply, finish(f); the scan's IMU report rides in f.imu
+// (Projection::handoff). checkSystemInitialization then adds imuPitchStart / imuRollStart to
+// transform_sum (FA:2329-2332), integrateTransformation ends in PluginIMURotation (FA:2557-2560) and
+// TransformToEnd runs its IMU tail (FA:1456-1483).
 template <class Cloud>
 class Odometry {
  public:
-  explicit Odometry(int32_t lidar, int32_t device = 0) : h_(lidar, device) {
+  explicit Odometry(int32_t lidar, int32_t device = 0, bool use_imu_undistortion = false)
+      : use_imu_undistortion(use_imu_undistortion), h_(lidar, device) {
     shadow_.resize(4 * 160);
     check(llsr_shadow_points(shadow_.data()), nullptr, "llsr_shadow_points");
   }
   llsr_handle* handle() const { return h_.get(); }
+  bool initialised() const { return inited_; }
 
   // one scan's features (moved from the channel's ProjectionOut): checkSystemInitialization on the
   // first scan (returns false: the `continue` at FA:2781-2784, finish must not follow), else
@@ -432,6 +456,7 @@ class Odometry {
       corner_last = std::move(f.corner_less_sharp);
       surf_last = std::move(f.surf_less_flat);
       append_xyzi(shadow_.data(), (int32_t)(shadow_.size() / 4), surf_last);
+      if (use_imu_undistortion) check(llsr_first_scan_imu(transform_sum, &f.imu), nullptr, "llsr_first_scan_imu");
       inited_ = true;
       return false;
     }
@@ -442,6 +467,16 @@ class Odometry {
   // integrateTransformation and publishCloudsLast's four TransformToEnd (FA:2792-2796) with whatever
   // transform_cur then holds
   void finish(FeatureClouds<Cloud>& f) {
+    if (use_imu_undistortion) {
+      check(llsr_integrate_transformation_imu(transform_sum, transform_cur, &f.imu), nullptr,
+            "llsr_integrate_transformation_imu");
+      transform_to_end_imu(transform_cur, f.imu, f.corner_less_sharp, corner_last);
+      transform_to_end_imu(transform_cur, f.imu, f.surf_less_flat, surf_last);
+      append_xyzi(shadow_.data(), (int32_t)(shadow_.size() / 4), surf_last);
+      transform_to_end_imu(transform_cur, f.imu, f.corner_sharp, corner_scan);
+      transform_to_end_imu(transform_cur, f.imu, f.surf_flat, surf_scan);
+      return;
+    }
     check(llsr_integrate_transformation(transform_sum, transform_cur), nullptr, "llsr_integrate_transformation");
     transform_to_end(transform_cur, f.corner_less_sharp, corner_last);
     transform_to_end(transform_cur, f.surf_less_flat, surf_last);
@@ -456,6 +491,7 @@ class Odometry {
     return true;
   }
 
+  const bool use_imu_undistortion;
   // FA's member state after the last step
   float transform_cur[6] = {0, 0, 0, 0, 0, 0};
   float transform_sum[6] = {0, 0, 0, 0, 0, 0};

@@ -340,6 +340,12 @@ extern "C" int32_t llsr_set_voxel_order(llsr_handle* h, int32_t order) {
   return LLSR_OK;
 }
 
+extern "C" int32_t llsr_set_imu_undistortion(llsr_handle* h, int32_t on) {
+  if (!h) return LLSR_EINVAL;
+  h->imu_undistortion = on != 0;
+  return LLSR_OK;
+}
+
 extern "C" int32_t llsr_reset_state(llsr_handle* h) {
   if (!h) return LLSR_EINVAL;
   HIP_OK(h, hipSetDevice(h->device));

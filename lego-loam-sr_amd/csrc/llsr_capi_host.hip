@@ -113,6 +113,42 @@ extern "C" int32_t llsr_transform_to_end(const float* transform_cur, const float
   return LLSR_OK;
 }
 
+// ---- the same with use_imu_undistortion == true: the functions k_odo_finish_imu runs (llsr_odo.h)
+extern "C" int32_t llsr_integrate_transformation_imu(float* transform_sum, const float* transform_cur,
+                                                     const llsr_imu_report* report) {
+  if (!transform_sum || !transform_cur || !report) return LLSR_EINVAL;
+  float ts[6], tc[6];
+  for (int k = 0; k < 6; ++k) { ts[k] = transform_sum[k]; tc[k] = transform_cur[k]; }
+  llsr::odo_integrate_imu(ts, tc, report->start, report->cur);
+  for (int k = 0; k < 6; ++k) transform_sum[k] = ts[k];
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_first_scan_imu(float* transform_sum, const llsr_imu_report* report) {
+  if (!transform_sum || !report) return LLSR_EINVAL;
+  llsr::odo_first_scan_imu(transform_sum, report->start);
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_transform_to_end_imu(const float* transform_cur, const llsr_imu_report* report,
+                                             const float* in_xyzi, int32_t n, float* out_xyzi) {
+  if (!transform_cur || !report || n < 0 || (n > 0 && (!in_xyzi || !out_xyzi))) return LLSR_EINVAL;
+  float tc[6];
+  for (int k = 0; k < 6; ++k) tc[k] = transform_cur[k];
+  llsr::OdoImuTail tail;
+  llsr::odo_imu_tail_set(tail, report->start, report->cur);
+  for (int32_t i = 0; i < n; ++i) {  // in place allowed: each row is read before it is written
+    const float* r = in_xyzi + 4 * (size_t)i;
+    const float4 q = llsr::odo_imu_tail(tail, llsr::odo_to_end(tc, make_float4(r[0], r[1], r[2], r[3])));
+    float* o = out_xyzi + 4 * (size_t)i;
+    o[0] = q.x;
+    o[1] = q.y;
+    o[2] = q.z;
+    o[3] = q.w;
+  }
+  return LLSR_OK;
+}
+
 // ---- /odom2 and updateInitialGuess (FA:354-383, 2337-2402): host-side scalar glue, llsr_odom_guess.h
 extern "C" int32_t llsr_odom_init(llsr_odom_state* st) {
   if (!st) return LLSR_EINVAL;

@@ -52,6 +52,9 @@ extern "C" int32_t llsr_odometry_reset(llsr_handle* h) {
 // llsr_odometry_batch (samples == nullptr) and llsr_odometry_batch_odom: with samples, transformSum
 // rides on the feature-count copy, updateInitialGuess (FA:2790) is evaluated on the host for the
 // flagged slots and k_odo_finish swaps it in after the LM.
+// With use_imu_undistortion (h->imu_undistortion) the guesses are evaluated and uploaded before the LM
+// launch, k_odo_inputs_imu stores them as the LM's start (the pre-LM updateInitialGuess, FA:2786-2788)
+// and k_odo_finish_imu reads the slots' IMU carry of this batch's feature stage.
 int32_t odo_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets, int32_t B,
                          const llsr_odom_sample* samples, const uint8_t* overwrite, void* hip_stream) {
   if (B < 1 || B > h->max_batch) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
@@ -118,7 +121,25 @@ int32_t odo_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets,
   a.scan_c = o.scan_c; a.scan_s = o.scan_s;
   a.tcur = o.tcur; a.tsum = o.tsum; a.inited = o.inited; a.frames = o.frames;
   if (samples) { a.guess = o.guess; a.flags = o.flags; a.tlm = o.tlm; }
-  k_odo_inputs<<<B, 256, 0, s>>>(a);
+  const bool imu = h->imu_undistortion;
+  // host-evaluated updateInitialGuess of the flagged slots (the same value before and after the LM:
+  // the sample and transformSum do not change in between)
+  auto upload_guesses = [&]() -> int32_t {
+    for (int b = 0; b < B; ++b) {
+      o.h_flags[b] = overwrite ? (overwrite[b] != 0) : 1;
+      if (o.h_flags[b]) llsr_odom::update_initial_guess(samples[b], o.h_tsum + 6 * b, o.h_guess + 6 * b);
+      else std::memset(o.h_guess + 6 * b, 0, sizeof(float) * 6);
+    }
+    HIP_OK(h, hipMemcpyAsync(o.guess, o.h_guess, sizeof(float) * 6 * B, hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(o.flags, o.h_flags, B, hipMemcpyHostToDevice, s));
+    return LLSR_OK;
+  };
+  if (imu) {
+    if (samples && (rc = upload_guesses()) != LLSR_OK) return rc;
+    k_odo_inputs_imu<<<B, 256, 0, s>>>(a);
+  } else {
+    k_odo_inputs<<<B, 256, 0, s>>>(a);
+  }
   HIP_OK(h, hipGetLastError());
   llsr_s2s_batch sb{};
   sb.n_problems = B;
@@ -132,16 +153,10 @@ int32_t odo_batch(llsr_handle* h, const float* d_xyzi, const int64_t* d_offsets,
   // the LM instantiation follows this batch's clouds, not the (high-water) reserve
   rc = s2s_launch(h, &sb, s, std::max(std::max(mMs, mF), 1), std::max(mNc, 1));
   if (rc != LLSR_OK) return rc;
-  if (samples) {  // evaluated while the LM runs: only k_odo_finish reads the guesses
-    for (int b = 0; b < B; ++b) {
-      o.h_flags[b] = overwrite ? (overwrite[b] != 0) : 1;
-      if (o.h_flags[b]) llsr_odom::update_initial_guess(samples[b], o.h_tsum + 6 * b, o.h_guess + 6 * b);
-      else std::memset(o.h_guess + 6 * b, 0, sizeof(float) * 6);
-    }
-    HIP_OK(h, hipMemcpyAsync(o.guess, o.h_guess, sizeof(float) * 6 * B, hipMemcpyHostToDevice, s));
-    HIP_OK(h, hipMemcpyAsync(o.flags, o.h_flags, B, hipMemcpyHostToDevice, s));
-  }
-  k_odo_finish<<<B, 256, 0, s>>>(a);
+  // evaluated while the LM runs: only k_odo_finish reads the guesses
+  if (samples && !imu && (rc = upload_guesses()) != LLSR_OK) return rc;
+  if (imu) k_odo_finish_imu<<<B, 256, 0, s>>>(a, h->imu.d_carry);
+  else k_odo_finish<<<B, 256, 0, s>>>(a);
   HIP_OK(h, hipGetLastError());
   HIP_OK(h, hipEventRecord(h->last_done, s));
   h->last_rec = true;

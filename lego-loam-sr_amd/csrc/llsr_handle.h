@@ -133,6 +133,9 @@ struct LLSR_HIDDEN llsr_handle {
     unsigned char* h_flags = nullptr;  // pinned [B]
     int cur = 0;                  // last_c/s[cur] hold the current last clouds
   } odo;
+  // use_imu_undistortion (llsr_set_imu_undistortion): the odometry launches k_odo_*_imu; a handle
+  // setting like dc.exact_vg, untouched by the reset calls
+  bool imu_undistortion = false;
   // mapping chain (llsr_mapping_*): MapOptimization's members per slot + the batch buffers
   struct MapSlot {
     llsr_mapping::MoPoses pose;

@@ -37,18 +37,23 @@ struct OdoArgs {
 
 __global__ void k_odo_inputs(OdoArgs a);
 __global__ void k_odo_finish(OdoArgs a);
+// use_imu_undistortion == true (llsr_set_imu_undistortion); carry: [max_batch] or nullptr
+__global__ void k_odo_inputs_imu(OdoArgs a);
+__global__ void k_odo_finish_imu(OdoArgs a, const llsr_imu_carry* carry);
 
 // The per-scan pose arithmetic of FA's end of scan, shared by k_odo_finish and the host entry points
 // llsr_transform_to_end / llsr_integrate_transformation (the FA node's thread calls those on its own
 // clouds). Float typing and operation order follow the reference lines; sin / cos / asin / atan2 are
-// the glibc ports of llsr_libm.h on both sides (use_imu_undistortion is false in every config block,
-// CFG:59/127/195).
+// the glibc ports of llsr_libm.h on both sides. The use_imu_undistortion == true branches (false in
+// the shipped config blocks, CFG:59/127/195; llsr_set_imu_undistortion) are the *_imu functions
+// below: k_odo_finish_imu and the llsr_*_imu host entry points.
 using llsr_libm::asinf_;
 using llsr_libm::atan2f_;
 using llsr_libm::cosf_;
 using llsr_libm::sinf_;
 
-// TransformToEnd (FA:1414-1490), use_imu_undistortion == false branch.
+// TransformToEnd (FA:1414-1490) up to (x6, y6, z6): all of it when use_imu_undistortion is false,
+// followed by odo_imu_tail when it is true.
 __host__ __device__ __forceinline__ float4 odo_to_end(const float* tc, float4 pi) {
   const float s = 10 * (pi.w - (float)trunc_i32(pi.w));
   float rx = s * tc[0], ry = s * tc[1], rz = s * tc[2];
@@ -113,5 +118,118 @@ __host__ __device__ __forceinline__ void odo_integrate(float* ts, const float* t
   ts[3] = tx; ts[4] = ty; ts[5] = tz;
 }
 
+// ---- use_imu_undistortion == true ----
+// What TransformToEnd's tail reads, once per scan: updateImuRollPitchYawStartSinCos (FA:491-498), the
+// cos / sin of imuYaw / Pitch / RollLast the reference evaluates per point (FA:1472-1481; the same
+// value for every point of the scan) and imuShiftFromStartX / Y / Z (always 0: ShiftToStartIMU is
+// never called).
+struct OdoImuTail {
+  float cos_start[3], sin_start[3];  // roll, pitch, yaw (imuRoll / Pitch / YawStart)
+  float cos_last[3], sin_last[3];    // roll, pitch, yaw (imuRoll / Pitch / YawLast)
+  float shift[3];                    // imuShiftFromStartX / Y / Z
+};
+
+// Entry k of the twelve: k < 6 the start cos (0..2) and sin (3..5), else the last cos (6..8) and sin
+// (9..11); start / last are llsr_imu_report's start / cur (roll, pitch, yaw).
+__host__ __device__ __forceinline__ float odo_imu_tail_entry(const float* start, const float* last, int k) {
+  const int j = k % 3;  // selects, not indexing: the callers' arrays stay in registers
+  const float a0 = k < 6 ? start[0] : last[0], a1 = k < 6 ? start[1] : last[1], a2 = k < 6 ? start[2] : last[2];
+  const float a = j == 0 ? a0 : (j == 1 ? a1 : a2);
+  return (k / 3) % 2 == 0 ? cosf_(a) : sinf_(a);
+}
+
+__host__ __device__ __forceinline__ void odo_imu_tail_set(OdoImuTail& t, const float* start, const float* last) {
+  for (int k = 0; k < 3; ++k) {
+    t.cos_start[k] = odo_imu_tail_entry(start, last, k);
+    t.sin_start[k] = odo_imu_tail_entry(start, last, 3 + k);
+    t.cos_last[k] = odo_imu_tail_entry(start, last, 6 + k);
+    t.sin_last[k] = odo_imu_tail_entry(start, last, 9 + k);
+    t.shift[k] = 0.f;
+  }
+}
+
+// TransformToEnd's tail (FA:1458-1483) of p = (x6, y6, z6, int(intensity)).
+__host__ __device__ __forceinline__ float4 odo_imu_tail(const OdoImuTail& t, float4 p) {
+  const float x7 = t.cos_start[0] * (p.x - t.shift[0]) - t.sin_start[0] * (p.y - t.shift[1]);
+  const float y7 = t.sin_start[0] * (p.x - t.shift[0]) + t.cos_start[0] * (p.y - t.shift[1]);
+  const float z7 = p.z - t.shift[2];
+  const float x8 = x7;
+  const float y8 = t.cos_start[1] * y7 - t.sin_start[1] * z7;
+  const float z8 = t.sin_start[1] * y7 + t.cos_start[1] * z7;
+  const float x9 = t.cos_start[2] * x8 + t.sin_start[2] * z8;
+  const float y9 = y8;
+  const float z9 = -t.sin_start[2] * x8 + t.cos_start[2] * z8;
+  const float x10 = t.cos_last[2] * x9 - t.sin_last[2] * z9;
+  const float y10 = y9;
+  const float z10 = t.sin_last[2] * x9 + t.cos_last[2] * z9;
+  const float x11 = x10;
+  const float y11 = t.cos_last[1] * y10 + t.sin_last[1] * z10;
+  const float z11 = -t.sin_last[1] * y10 + t.cos_last[1] * z10;
+  return make_float4(t.cos_last[0] * x11 + t.sin_last[0] * y11, -t.sin_last[0] * x11 + t.cos_last[0] * y11, z11,
+                     p.w);
+}
+
+// PluginIMURotation (FA:1492-1550); ac* may alias bc* (the sines and cosines are taken first).
+__host__ __device__ inline void odo_plugin_imu_rotation(float bcx, float bcy, float bcz, float blx, float bly,
+                                                        float blz, float alx, float aly, float alz, float& acx,
+                                                        float& acy, float& acz) {
+  const float sbcx = sinf_(bcx), cbcx = cosf_(bcx), sbcy = sinf_(bcy), cbcy = cosf_(bcy);
+  const float sbcz = sinf_(bcz), cbcz = cosf_(bcz);
+  const float sblx = sinf_(blx), cblx = cosf_(blx), sbly = sinf_(bly), cbly = cosf_(bly);
+  const float sblz = sinf_(blz), cblz = cosf_(blz);
+  const float salx = sinf_(alx), calx = cosf_(alx), saly = sinf_(aly), caly = cosf_(aly);
+  const float salz = sinf_(alz), calz = cosf_(alz);
+
+  const float srx = -sbcx*(salx*sblx + calx*caly*cblx*cbly + calx*cblx*saly*sbly)
+                  - cbcx*cbcz*(calx*saly*(cbly*sblz - cblz*sblx*sbly)
+                  - calx*caly*(sbly*sblz + cbly*cblz*sblx) + cblx*cblz*salx)
+                  - cbcx*sbcz*(calx*caly*(cblz*sbly - cbly*sblx*sblz)
+                  - calx*saly*(cbly*cblz + sblx*sbly*sblz) + cblx*salx*sblz);
+  acx = -asinf_(srx);
+
+  const float srycrx = (cbcy*sbcz - cbcz*sbcx*sbcy)*(calx*saly*(cbly*sblz - cblz*sblx*sbly)
+                     - calx*caly*(sbly*sblz + cbly*cblz*sblx) + cblx*cblz*salx)
+                     - (cbcy*cbcz + sbcx*sbcy*sbcz)*(calx*caly*(cblz*sbly - cbly*sblx*sblz)
+                     - calx*saly*(cbly*cblz + sblx*sbly*sblz) + cblx*salx*sblz)
+                     + cbcx*sbcy*(salx*sblx + calx*caly*cblx*cbly + calx*cblx*saly*sbly);
+  const float crycrx = (cbcz*sbcy - cbcy*sbcx*sbcz)*(calx*caly*(cblz*sbly - cbly*sblx*sblz)
+                     - calx*saly*(cbly*cblz + sblx*sbly*sblz) + cblx*salx*sblz)
+                     - (sbcy*sbcz + cbcy*cbcz*sbcx)*(calx*saly*(cbly*sblz - cblz*sblx*sbly)
+                     - calx*caly*(sbly*sblz + cbly*cblz*sblx) + cblx*cblz*salx)
+                     + cbcx*cbcy*(salx*sblx + calx*caly*cblx*cbly + calx*cblx*saly*sbly);
+  acy = atan2f_(srycrx / cosf_(acx), crycrx / cosf_(acx));
+
+  const float srzcrx = sbcx*(cblx*cbly*(calz*saly - caly*salx*salz)
+                     - cblx*sbly*(caly*calz + salx*saly*salz) + calx*salz*sblx)
+                     - cbcx*cbcz*((caly*calz + salx*saly*salz)*(cbly*sblz - cblz*sblx*sbly)
+                     + (calz*saly - caly*salx*salz)*(sbly*sblz + cbly*cblz*sblx)
+                     - calx*cblx*cblz*salz) + cbcx*sbcz*((caly*calz + salx*saly*salz)*(cbly*cblz
+                     + sblx*sbly*sblz) + (calz*saly - caly*salx*salz)*(cblz*sbly - cbly*sblx*sblz)
+                     + calx*cblx*salz*sblz);
+  const float crzcrx = sbcx*(cblx*sbly*(caly*salz - calz*salx*saly)
+                     - cblx*cbly*(saly*salz + caly*calz*salx) + calx*calz*sblx)
+                     + cbcx*cbcz*((saly*salz + caly*calz*salx)*(sbly*sblz + cbly*cblz*sblx)
+                     + (caly*salz - calz*salx*saly)*(cbly*sblz - cblz*sblx*sbly)
+                     + calx*calz*cblx*cblz) - cbcx*sbcz*((saly*salz + caly*calz*salx)*(cblz*sbly
+                     - cbly*sblx*sblz) + (caly*salz - calz*salx*saly)*(cbly*cblz + sblx*sbly*sblz)
+                     - calx*calz*cblx*sblz);
+  acz = atan2f_(srzcrx / cosf_(acx), crzcrx / cosf_(acx));
+}
+
+// integrateTransformation (FA:2537-2568) with use_imu_undistortion: the translation comes from the
+// un-plugged rotation, then PluginIMURotation(rx, ry, rz, imuPitch / Yaw / RollStart,
+// imuPitch / Yaw / RollLast). start / last: roll, pitch, yaw.
+__host__ __device__ inline void odo_integrate_imu(float* ts, const float* tc, const float* start, const float* last) {
+  odo_integrate(ts, tc);
+  float rx, ry, rz;
+  odo_plugin_imu_rotation(ts[0], ts[1], ts[2], start[1], start[2], start[0], last[1], last[2], last[0], rx, ry, rz);
+  ts[0] = rx; ts[1] = ry; ts[2] = rz;
+}
+
+// checkSystemInitialization's add on a slot's first scan (FA:2329-2332).
+__host__ __device__ __forceinline__ void odo_first_scan_imu(float* ts, const float* start) {
+  ts[0] += start[1];
+  ts[2] += start[0];
+}
 
 }  // namespace llsr

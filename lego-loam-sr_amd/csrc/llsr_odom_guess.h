@@ -5,9 +5,9 @@
 // sincos / atan2 / sqrt, the functions the reference itself calls.
 //   * odomCallback (FA:354-383): tf2 getRPY of the message orientation, position relative to the
 //     first message;
-//   * updateInitialGuess (FA:2370-2402; the IMU member copies at FA:2339-2349 are dead with
-//     use_imu_undistortion false in every config block): transformCur rebuilt from the latest
-//     /odom2 sample and transformSum.
+//   * updateInitialGuess (FA:2370-2402): transformCur rebuilt from the latest /odom2 sample and
+//     transformSum. Its IMU member copies (FA:2339-2349) need no state here: with
+//     use_imu_undistortion on, k_odo_finish_imu reads the scan's imu*Cur as imu*Last.
 // Evaluation order restated here (unpinned: neither Eigen nor tf2 is available to
 // check against):
 //   * AngleAxisd * AngleAxisd * AngleAxisd is (Quaterniond(a) * Quaterniond(b)) * Quaterniond(c)

@@ -53,7 +53,8 @@ EXPORTS = [
     "llsr_icp_align_host", "llsr_icp_create", "llsr_icp_destroy", "llsr_icp_last_error", "llsr_icp_align",
     "llsr_icp_last_times", "llsr_map_loop_submaps", "llsr_map_loop_closure",
     "llsr_imu_init", "llsr_imu_callback", "llsr_imu_scan_window", "llsr_imu_deskew_host", "llsr_stage_imu",
-    "llsr_fetch_imu_report",
+    "llsr_fetch_imu_report", "llsr_set_imu_undistortion", "llsr_integrate_transformation_imu",
+    "llsr_transform_to_end_imu", "llsr_first_scan_imu",
 ]
 
 
@@ -141,6 +142,11 @@ def lib():
                                            C.POINTER(_abi.ImuReport)]
         L.llsr_stage_imu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
         L.llsr_fetch_imu_report.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_abi.ImuReport)]
+        L.llsr_set_imu_undistortion.argtypes = [C.c_void_p, C.c_int32]
+        L.llsr_integrate_transformation_imu.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.ImuReport)]
+        L.llsr_transform_to_end_imu.argtypes = [C.c_void_p, C.POINTER(_abi.ImuReport), C.c_void_p, C.c_int32,
+                                                C.c_void_p]
+        L.llsr_first_scan_imu.argtypes = [C.c_void_p, C.POINTER(_abi.ImuReport)]
         L.llsr_map_config_default.argtypes = [C.POINTER(_abi.MapConfig)]
         L.llsr_map_config_lidar.argtypes = [C.POINTER(_abi.MapConfig), C.c_int32]
         L.llsr_map_create.argtypes = [C.POINTER(_abi.MapConfig), C.c_int32]
@@ -259,6 +265,11 @@ class Pipeline:
         """_abi.LLSR_VOXEL_ORDER_PCL (default: the reference's std::sort order) or LLSR_VOXEL_ORDER_INPUT
         (ring order inside each voxel) for the less-flat VoxelGrid."""
         self._check(lib().llsr_set_voxel_order(self._h, order), "llsr_set_voxel_order")
+
+    def set_imu_undistortion(self, on: bool):
+        """llsr_set_imu_undistortion: the reference's use_imu_undistortion switch for this handle's
+        odometry (default off; takes effect at the next batch, kept across the reset calls)."""
+        self._check(lib().llsr_set_imu_undistortion(self._h, 1 if on else 0), "llsr_set_imu_undistortion")
 
     def process_scan(self, xyzi: np.ndarray) -> dict:
         xyzi = np.ascontiguousarray(xyzi, dtype=np.float32).reshape(-1, 4)
@@ -738,22 +749,57 @@ def shadow_points() -> np.ndarray:
     return out
 
 
-def integrate_transformation(transform_sum, transform_cur) -> np.ndarray:
-    """integrateTransformation (FA:2537-2568) on the host side of the library: the new transformSum."""
+def _imu_report(imu) -> "_abi.ImuReport":
+    """An _abi.ImuReport from one, or from a {field: [3]} mapping as fetch_imu_report returns it
+    (missing fields are zero; the use_imu_undistortion branches read `start` and `cur`)."""
+    if isinstance(imu, _abi.ImuReport):
+        return imu
+    r = _abi.ImuReport()
+    for f, _ in _abi.ImuReport._fields_:
+        if f in imu:
+            v = np.asarray(imu[f], np.float32).reshape(3)
+            setattr(r, f, (C.c_float * 3)(*(float(x) for x in v)))
+    return r
+
+
+def integrate_transformation(transform_sum, transform_cur, imu=None) -> np.ndarray:
+    """integrateTransformation (FA:2537-2568) on the host side of the library: the new transformSum.
+    imu: the scan's IMU report (use_imu_undistortion == true: PluginIMURotation at the end)."""
     ts = np.array(transform_sum, np.float32).reshape(6).copy()
     tc = np.ascontiguousarray(transform_cur, np.float32).reshape(6)
-    rc = lib().llsr_integrate_transformation(ts.ctypes.data, tc.ctypes.data)
+    if imu is None:
+        rc = lib().llsr_integrate_transformation(ts.ctypes.data, tc.ctypes.data)
+    else:
+        rc = lib().llsr_integrate_transformation_imu(ts.ctypes.data, tc.ctypes.data, C.byref(_imu_report(imu)))
     if rc != 0:
         raise LlsrError(f"llsr_integrate_transformation: {rc}")
     return ts
 
 
-def transform_to_end(transform_cur, xyzi) -> np.ndarray:
-    """TransformToEnd (FA:1414-1490) of float4 rows on the host side of the library."""
+def first_scan_imu(transform_sum, imu) -> np.ndarray:
+    """checkSystemInitialization's use_imu_undistortion add (FA:2329-2332): the new transformSum."""
+    ts = np.array(transform_sum, np.float32).reshape(6).copy()
+    rc = lib().llsr_first_scan_imu(ts.ctypes.data, C.byref(_imu_report(imu)))
+    if rc != 0:
+        raise LlsrError(f"llsr_first_scan_imu: {rc}")
+    return ts
+
+
+def transform_to_end(transform_cur, xyzi, imu=None, out=None) -> np.ndarray:
+    """TransformToEnd (FA:1414-1490) of float4 rows on the host side of the library. imu: the scan's
+    IMU report (use_imu_undistortion == true: the tail at FA:1456-1483); out: the array to write
+    (may be xyzi itself when that is a contiguous float32 array)."""
     tc = np.ascontiguousarray(transform_cur, np.float32).reshape(6)
     a = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
-    out = np.empty_like(a)
-    rc = lib().llsr_transform_to_end(tc.ctypes.data, a.ctypes.data, len(a), out.ctypes.data)
+    if out is None:
+        out = np.empty_like(a)
+    elif out.dtype != np.float32 or not out.flags.c_contiguous or out.size != a.size:
+        raise ValueError("out: a contiguous float32 array of the input's size")
+    if imu is None:
+        rc = lib().llsr_transform_to_end(tc.ctypes.data, a.ctypes.data, len(a), out.ctypes.data)
+    else:
+        rc = lib().llsr_transform_to_end_imu(tc.ctypes.data, C.byref(_imu_report(imu)), a.ctypes.data, len(a),
+                                             out.ctypes.data)
     if rc != 0:
         raise LlsrError(f"llsr_transform_to_end: {rc}")
     return out
