@@ -74,6 +74,20 @@ typedef struct llsr_config {
   int32_t mode;                    /* LLSR_MODE_* */
 } llsr_config;
 
+/* Configurations llsr_create refuses with LLSR_EINVAL, before it looks for a device: those for
+ * which the reference's arithmetic defines no result.
+ *  - num_vertical_scans outside 2..64 or num_horizontal_scans outside 16..2048;
+ *  - a float field that is not finite (NaN or +-Inf), whichever field it is;
+ *  - vertical_angle_top <= vertical_angle_bottom: the vertical resolution is 0 or negative, and the
+ *    row formula divides by it (IP:117-121, 313-316);
+ *  - scan_period <= 0;
+ *  - segment_theta outside the open interval (0, 90) deg: tan() of it is the segmentation
+ *    threshold (IP:849);
+ *  - use_vlp32c with more than 512 elevation bins (below).
+ * Every other value is accepted and computes what the reference's code computes with it:
+ * ground_scan_index >= num_vertical_scans (no row lies above it: no outlier), thresholds of 0 or
+ * below, segment_valid_point_num above 30 (the line test is then dead), use_kitti on any H. */
+
 /* use_vlp32c (IP:349-427, 567-568). A point's row is not computed from its elevation: every
  * finite point of the scan falls into the 0.335 deg elevation bin
  *   temp = int((asinf(z / range) + ang_bottom) / (0.335 * DEG_TO_RAD)),

@@ -192,13 +192,28 @@ static void mt_first_state(uint32_t* m) {
   }
 }
 
+// The configurations the reference's arithmetic defines no result for (include/llsr.h, next to
+// llsr_config): host-only, so llsr_create refuses them before it looks for a device.
+static bool config_defined(const llsr_config& c) {
+  if (c.num_vertical_scans < 2 || c.num_vertical_scans > 64 || c.num_horizontal_scans < 16 ||
+      c.num_horizontal_scans > 2048)
+    return false;
+  const float f[] = {c.vertical_angle_bottom, c.vertical_angle_top, c.sensor_mount_angle, c.segment_theta,
+                     c.scan_period, c.edge_threshold, c.surf_threshold, c.nearest_feature_search_distance,
+                     c.DBFr, c.RatioXY, c.RatioZ, c.step_size, c.stop_thres};
+  for (float v : f)
+    if (!std::isfinite(v)) return false;
+  if (!(c.vertical_angle_top > c.vertical_angle_bottom)) return false;  // resolution 0: IP:313-316 divides by it
+  if (!(c.scan_period > 0.0f)) return false;
+  if (!(c.segment_theta > 0.0f && c.segment_theta < 90.0f)) return false;  // tan() of it: IP:849
+  return true;
+}
+
 extern "C" int32_t llsr_create(const llsr_config* cfg, int32_t hip_device, int32_t max_batch,
                                int32_t max_points, llsr_handle** out) {
   if (!cfg || !out || max_batch < 1 || max_points < 1) return LLSR_EINVAL;
   *out = nullptr;
-  if (cfg->num_vertical_scans < 2 || cfg->num_vertical_scans > 64 || cfg->num_horizontal_scans < 16 ||
-      cfg->num_horizontal_scans > 2048)
-    return LLSR_EINVAL;
+  if (!config_defined(*cfg)) return LLSR_EINVAL;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= hip_device || hip_device < 0) return LLSR_ENODEV;
   // every error exit below releases what was acquired so far with the handle (its members own it)
