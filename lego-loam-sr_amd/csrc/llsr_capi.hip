@@ -654,6 +654,56 @@ extern "C" int32_t llsr_debug_exact_sort32(const uint32_t* ranks, int32_t n, int
   return LLSR_OK;
 }
 
+// Diagnostics (not part of the ABI header): the DBSCAN merge and its run-length filter as a batch
+// runs them (k_dbscan_merge<kDbL>, kDbL 1024 or 2048) over n independent neighbourhood relations
+// given as host bit rows adj[n][kAdjCap][kAdjWords] (row i, bit j: j is a neighbour of i; only rows
+// below M[k] and the two words of every 64-point chunk below M[k] are read, as k_dbscan_adj writes
+// them), M[k] <= kDbL. less_sharp[a] = a, so sharp[n][kAdjCap] returns positions; cluster is
+// [n][kAdjCap] too, entries past M[k] / n_sharp[k] are -1. For tests/test_gpu_dbscan_merge.py.
+extern "C" int32_t llsr_debug_dbscan_merge(const uint32_t* adj, const int32_t* M, int32_t n, int32_t kDbL,
+                                           int32_t* cluster, int32_t* sharp, int32_t* n_sharp) {
+  if (!adj || !M || !cluster || !sharp || !n_sharp || n < 1 || n > 1024 || (kDbL != 1024 && kDbL != 2048))
+    return LLSR_EINVAL;
+  for (int32_t k = 0; k < n; ++k)
+    if (M[k] < 0 || M[k] > kDbL) return LLSR_EINVAL;
+  const size_t HW = kAdjCap, nadj = (size_t)n * kAdjCap * kAdjWords;
+  std::vector<int> cnt((size_t)n * kCnt, 0), pos((size_t)n * HW);
+  for (int32_t k = 0; k < n; ++k) {
+    cnt[(size_t)k * kCnt + C_M] = M[k];
+    for (size_t a = 0; a < HW; ++a) pos[k * HW + a] = (int)a;
+  }
+  llsr_host::DevMem dadj, dcnt, dpos, dcl, dsh;
+  if (llsr_host::alloc(dadj, sizeof(uint32_t) * nadj) != hipSuccess ||
+      llsr_host::alloc(dcnt, sizeof(int) * cnt.size()) != hipSuccess ||
+      llsr_host::alloc(dpos, sizeof(int) * n * HW) != hipSuccess ||
+      llsr_host::alloc(dcl, sizeof(int) * n * HW) != hipSuccess ||
+      llsr_host::alloc(dsh, sizeof(int) * n * HW) != hipSuccess)
+    return LLSR_ENODEV;
+  if (hipMemcpy(dadj, adj, sizeof(uint32_t) * nadj, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(dcnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(dpos, pos.data(), sizeof(int) * n * HW, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(dcl, 0xff, sizeof(int) * n * HW) != hipSuccess ||
+      hipMemset(dsh, 0xff, sizeof(int) * n * HW) != hipSuccess)
+    return LLSR_EIO;
+  DevCfg c{};
+  c.HW = (int)HW;
+  DevBufs d{};  // the fields the kernel reads at M <= kDbL
+  d.counts = static_cast<int*>(dcnt.get());
+  d.db_adj = static_cast<uint32_t*>(dadj.get());
+  d.less_sharp = static_cast<int*>(dpos.get());
+  d.cluster = static_cast<int*>(dcl.get());
+  d.sharp = static_cast<int*>(dsh.get());
+  if (kDbL == 1024) k_dbscan_merge<1024><<<n, 64>>>(c, d);
+  else k_dbscan_merge<2048><<<n, 64>>>(c, d);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(cluster, dcl, sizeof(int) * n * HW, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(sharp, dsh, sizeof(int) * n * HW, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(cnt.data(), dcnt, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return LLSR_EIO;
+  for (int32_t k = 0; k < n; ++k) n_sharp[k] = cnt[(size_t)k * kCnt + C_SHARP];
+  return LLSR_OK;
+}
+
 // Diagnostics (not part of the ABI header): adjustDistortion's halfPassed test (FA:578-586) as
 // k_segment evaluates it, for n (y, x, start) triples: out[3 i] = the certified fast test's code
 // (0 fails, 1 passes, 2 undecided), out[3 i + 1] = its decision with the exact fallback, out[3 i + 2] =

@@ -1252,19 +1252,20 @@ __global__ __launch_bounds__(256) void k_dbscan_adj(DevCfg c, DevBufs d, const f
 // ---------------------------------------------------------------------------------------------
 // K9c DBSCAN merge (FA:1342-1386) + cluster run-length filter (FA:1281-1305), ONE WAVE per scan.
 // The reference relabels every point whose label is in the neighbours' label list, including
-// label 0 (so all still-unlabelled points collapse into min_label). That is a merge of label
-// classes, done here with a union-find over label nodes 1..M plus "zero" nodes: Z0 holds every
-// not-yet-visited point, and visiting i moves i into a fresh zero node (cluster[i] = 0). A merge
-// unions the neighbours' classes — and, when a neighbour is unlabelled, every live zero class —
-// into min_label; a new label only re-points the neighbours. Checked against a literal
-// transcription of the loop in tests/test_dbscan_uf.py. Per point: O(degree) work.
+// label 0 (so all still-unlabelled points collapse into min_label).
+//
+// Small scans (k_dbscan_merge's kDbRegs: every VLP-16-sized scan): the literal loop with cluster[]
+// in registers. Lane l owns cluster[l + 64 e]; the neighbour flag of an owned element is one bit of
+// the row word 2 e + (l >> 5), min_label is a wave min, and the relabelling is a compare and select
+// per owned element, once per distinct neighbour label. No memory access sits on the label chain:
+// row i + 1's words are read from the staged block while point i is labelled.
+//
+// Larger scans: a merge of label classes in LDS or global memory, a union-find over label nodes 1..M plus
+// "zero" nodes: Z0 holds every not-yet-visited point, and visiting i moves i into a fresh zero node
+// (cluster[i] = 0). A merge unions the neighbours' classes — and, when a neighbour is unlabelled,
+// every live zero class — into min_label; a new label only re-points the neighbours. Checked
+// against a literal transcription of the loop in tests/test_dbscan_uf.py. Per point: O(degree) work.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-template <bool lds>
 __device__ __forceinline__ int uf_root(int* par, int x) {  // path halving
   while (true) {
     const int p = par[x];
@@ -1276,31 +1277,191 @@ __device__ __forceinline__ int uf_root(int* par, int x) {  // path halving
   }
 }
 
-// Minimum of v over lanes with `valid`, for 0 <= v < 2^nbits, by ballots (scalar work only);
-// returns 999999999 when no lane is valid.
-__device__ __forceinline__ int wave_min_ballot(int v, bool valid, int nbits) {
-  unsigned long long cand = __ballot(valid);
-  if (!cand) return 999999999;
-  const int l = lane_id();
-  int res = 0;
-  for (int bt = nbits - 1; bt >= 0; --bt) {
-    const unsigned long long z = __ballot(((cand >> l) & 1ull) && !((v >> bt) & 1));
-    if (z) cand = z;
-    else res |= 1 << bt;
-  }
-  return res;
-}
-
-
 // kRowBlk adjacency rows are staged into LDS per block (one load latency per block instead of one
 // per point: the rows of a 300-point scan come from L2 / the Infinity Cache, ~1 us away), the next
-// block's words waiting in registers (kPF per lane) while the current one is merged.
+// block's words waiting in registers while the current one is merged.
 constexpr int kRowBlk = 32;
 
+// Wave minimum of unsigned values by DPP: a min scan along each row of 16 lanes (row_shr 1, 2, 4,
+// 8), then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3; lanes without a
+// source keep the identity. The result is lane 63's.
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+  uint32_t t;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false); v = t < v ? t : v;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false); v = t < v ? t : v;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false); v = t < v ? t : v;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false); v = t < v ? t : v;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false); v = t < v ? t : v;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false); v = t < v ? t : v;
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// The register-resident merge for ceil(M / 64) <= NE. rowbuf: kRowBlk rows of 2 NE words; hist:
+// 64 NE + 1 label counts; keep: a bitmap of 64 NE + 2 labels. Lane l owns the NE elements
+// l + 64 e, all of them with no guard: the loops over e are straight-line code, lab[] and the row
+// words stay in registers, and an element at or past M is nobody's neighbour (k_dbscan_adj leaves
+// its bits zero; the words past the last 64-point chunk, which it does not write, are staged as
+// zero). Such an element only ever follows the zeros' collapse and is never written out.
+template <int NE>
+__device__ __forceinline__ void dbscan_merge_regs(const DevBufs& d, size_t base, int b, int M, uint32_t* rowbuf,
+                                                  int* hist, uint32_t* keep) {
+  constexpr int W32 = 2 * NE;  // staged words per row
+  const int l = lane_id();
+  const unsigned long long lt = (1ull << l) - 1ull;
+  const int nW = 2 * ((M + 63) >> 6);  // row words k_dbscan_adj writes: both of every 64-point chunk
+  const uint32_t* adj = d.db_adj + (size_t)b * kAdjCap * kAdjWords;
+  const int hi = l >> 5;
+  const uint32_t bit = 1u << (l & 31);
+  uint32_t pf[NE];  // a block is kRowBlk * W32 = 64 NE words
+  auto fetch_block = [&](int blk) __attribute__((always_inline)) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+      const int idx = l + 64 * e;
+      const int r = idx / W32, w = idx % W32;
+      const int row = blk * kRowBlk + r;
+      pf[e] = (w < nW && row < M) ? adj[(size_t)row * kAdjWords + w] : 0u;
+    }
+  };
+  // block blk's words from the registers into LDS, block blk + 1's loads into flight
+  auto stage_block = [&](int blk) __attribute__((always_inline)) {
+    wave_order();  // after the reads of the block before
+#pragma unroll
+    for (int e = 0; e < NE; ++e) rowbuf[l + 64 * e] = pf[e];
+    wave_order();
+    fetch_block(blk + 1);
+  };
+  // this lane's word of every owned element of the staged row i: two addresses per read
+  auto read_row = [&](int i, uint32_t (&w)[NE]) __attribute__((always_inline)) {
+    const uint32_t* r = rowbuf + (i % kRowBlk) * W32 + hi;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) w[e] = r[2 * e];
+  };
+  int lab[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) lab[e] = 0;
+  int label = 0;
+  // one visit of FA:1342-1386: rw = row i's words, rn receives row i + 1's
+  auto visit = [&](int i, const uint32_t (&rw)[NE], uint32_t (&rn)[NE]) __attribute__((always_inline)) {
+    if (i + 1 < M) {
+      if ((i + 1) % kRowBlk == 0) stage_block((i + 1) / kRowBlk);
+      read_row(i + 1, rn);
+    }
+    // cluster[i] = 0; the neighbour flags; min_label over the labelled neighbours (label - 1 as
+    // unsigned puts 0 last)
+    bool nb[NE];
+    uint32_t m = 0xffffffffu;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+      if (l + 64 * e == i) lab[e] = 0;
+      nb[e] = (rw[e] & bit) != 0u;
+      const uint32_t v = nb[e] ? (uint32_t)lab[e] - 1u : 0xffffffffu;
+      m = v < m ? v : m;
+    }
+    m = wave_min_u32(m);
+    const int mn = m == 0xffffffffu ? 999999999 : (int)(m + 1u);
+    if (mn <= label) {
+      // every element whose label is in the neighbours' label list becomes min_label. Only
+      // x -> min_label happens, so testing against the current labels equals testing against the
+      // labels before the visit, in any order of the distinct values; min_label itself is a no-op.
+      // So: while a neighbour's label is not min_label, take one such label and relabel its class.
+      while (true) {
+        int cand = 0;
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+          const bool p = nb[e] & (lab[e] != mn);
+          cand = p ? lab[e] : cand;
+          any |= p;
+        }
+        const unsigned long long pm = __ballot(any);
+        if (!pm) break;
+        const int L = __builtin_amdgcn_readlane(cand, __builtin_ctzll(pm));
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+          if (lab[e] == L) lab[e] = mn;
+      }
+    } else {
+      label += 1;
+#pragma unroll
+      for (int e = 0; e < NE; ++e)
+        if (nb[e]) lab[e] = label;
+    }
+  };
+  uint32_t ra[NE], rb[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) ra[e] = rb[e] = 0u;
+  if (M > 0) {
+    fetch_block(0);
+    stage_block(0);
+    read_row(0, ra);
+  }
+  for (int i = 0; i < M; i += 2) {
+    visit(i, ra, rb);
+    if (i + 1 < M) visit(i + 1, rb, ra);
+  }
+  // ---- the output array; run lengths of the sorted labels, last run dropped; keep label r+1 if
+  // run r >= 4 ----
+  const int NL = label + 1;
+  for (int q = l; q < NL; q += 64) hist[q] = 0;
+  wave_order();
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const int a = l + 64 * e;
+    if (a < M) {
+      d.cluster[base + a] = lab[e];
+      atomicAdd(&hist[lab[e]], 1);
+    }
+  }
+  wave_order();
+  int lmax = -1;
+  for (int q = l; q < NL; q += 64)
+    if (hist[q] > 0) lmax = q;
+  lmax = wave_reduce_max(lmax);
+  const int nwLb = (NL + 1 + 31) / 32;
+  for (int w = l; w < nwLb; w += 64) keep[w] = 0u;
+  wave_order();
+  int run = 0;
+  for (int q0 = 0; q0 < NL; q0 += 64) {
+    const int q = q0 + l;
+    const bool pres = q < NL && hist[q] > 0;
+    const unsigned long long m = __ballot(pres);
+    const int r = run + __popcll(m & lt);
+    if (pres && q != lmax && hist[q] >= 4 && r + 1 < NL) atomicOr(&keep[(r + 1) >> 5], 1u << ((r + 1) & 31));
+    run += __popcll(m);
+  }
+  wave_order();
+  int ns = 0;
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const int a = l + 64 * e;
+    const bool kp = a < M && ((keep[lab[e] >> 5] >> (lab[e] & 31)) & 1u);
+    const unsigned long long m = __ballot(kp);
+    if (kp) d.sharp[base + ns + __popcll(m & lt)] = d.less_sharp[base + a];
+    ns += __popcll(m);
+  }
+  if (l == 0) d.counts[b * kCnt + C_SHARP] = ns;
+}
+
+// The narrowest instantiation that holds the scan, chosen per scan: 1 to 8 owned elements per lane
+// one by one (VLP-16-sized scans, M ~ 300, run with 5), then 12, 16, ... up to kDbL / 64.
+template <int kDbL, int NE = 1>
+__device__ __forceinline__ void dbscan_merge_dispatch(const DevBufs& d, size_t base, int b, int M, uint32_t* rowbuf,
+                                                      int* hist, uint32_t* keep) {
+  if constexpr (64 * NE >= kDbL) {
+    dbscan_merge_regs<NE>(d, base, b, M, rowbuf, hist, keep);
+  } else {
+    if (M <= 64 * NE) dbscan_merge_regs<NE>(d, base, b, M, rowbuf, hist, keep);
+    else dbscan_merge_dispatch<kDbL, (NE < 8 ? NE + 1 : NE + 4)>(d, base, b, M, rowbuf, hist, keep);
+  }
+}
+
+// The union-find merge: par 2 M + 3, raw M, nb M, rt M + 1, live M + 1, shn 1, in global memory
+// (M > kDbL) or in LDS (lds: scans above kDbRegs points, where a visit's O(degree) work beats the
+// register form's O(M / 64); the rows then staged in rowbuf, kPF words per lane).
 template <bool lds, int kPF = 1>
-__device__ __forceinline__ void dbscan_merge(const DevCfg& c, const DevBufs& d, size_t base, int b, int M,
-                                             int* par, int* raw, int* nb, int* rt, int* live, int* shn,
-                                             uint32_t* rowbuf = nullptr) {
+__device__ __forceinline__ void dbscan_merge_uf(const DevCfg& c, const DevBufs& d, size_t base, int b, int M,
+                                                int* par, int* raw, int* nb, int* rt, int* live, int* shn,
+                                                uint32_t* rowbuf = nullptr) {
   auto sync_ = [&]() {
     if (lds) wave_order();
     else __threadfence_block();
@@ -1381,7 +1542,7 @@ __device__ __forceinline__ void dbscan_merge(const DevCfg& c, const DevBufs& d, 
     int lmin = 999999999;
     bool zero = false;
     for (int k = l; k < deg; k += 64) {
-      const int r = uf_root<lds>(par, raw[nb[k]]);
+      const int r = uf_root(par, raw[nb[k]]);
       rt[k] = r;
       if (r > M) zero = true;
       else if (r < lmin) lmin = r;
@@ -1399,7 +1560,7 @@ __device__ __forceinline__ void dbscan_merge(const DevCfg& c, const DevBufs& d, 
         const int nl = shn[0];
         for (int k = l; k <= nl; k += 64) {
           const int z = k < nl ? live[k] : zi;
-          const int r = uf_root<lds>(par, z);
+          const int r = uf_root(par, z);
           if (r > M) par[r] = lmin;
         }
         sync_();
@@ -1420,7 +1581,7 @@ __device__ __forceinline__ void dbscan_merge(const DevCfg& c, const DevBufs& d, 
   }
   // final labels -> raw (as CL) and the output array
   for (int j = l; j < M; j += 64) {
-    const int r = uf_root<lds>(par, raw[j]);
+    const int r = uf_root(par, raw[j]);
     const int v = r > M ? 0 : r;
     d.cluster[base + j] = v;
     nb[j] = v;
@@ -1463,26 +1624,35 @@ __device__ __forceinline__ void dbscan_merge(const DevCfg& c, const DevBufs& d, 
   if (l == 0) d.counts[b * kCnt + C_SHARP] = ns;
 }
 
-// One wave per scan, so the LDS footprint sets how many scans a CU runs at once: kDbL = 1024
-// (24.6 KB, VLP-16-sized scans, M ~ 300) fits every SIMD of a CU; 2048 (49 KB) serves HDL-64E.
+// One wave per scan, so the LDS footprint sets how many scans a CU runs at once.
+// kDbL = 1024 (VLP-16-sized scans, M ~ 300): every scan takes the register form, and the LDS is the
+// staged row block, the label counts and the keep bitmap, 8.3 KB: 8 waves of a CU, 2048 scans of a
+// batch on 256 CUs, run at once and leave LDS to the kernels of the other streams.
+// kDbL = 2048 (HDL-64E): the register form's visit costs O(M / 64) instructions and measured slower
+// than the union-find's O(degree) at HDL-64E's M (2.1 against 1.4 ms per 512 scans), so it serves
+// scans of at most kDbRegs points there and larger ones keep the union-find in LDS (57 KB).
 template <int kDbL>
 __global__ __launch_bounds__(64) void k_dbscan_merge(DevCfg c, DevBufs d) {
-  constexpr int kPF = kRowBlk * (kDbL / 32) / 64;  // staged words per lane (M <= kDbL)
+  constexpr bool kUf = kDbL > 1024;                // an LDS union-find path besides the register form
+  constexpr int kDbRegs = kUf ? 512 : kDbL;        // largest M of the register form
+  constexpr int kPF = kRowBlk * (kDbL / 32) / 64;  // staged words per lane of the union-find (M <= kDbL)
   __shared__ uint32_t sRows[kRowBlk * (kDbL / 32)];
-  __shared__ int sPar[2 * kDbL + 4];
-  __shared__ int sRaw[kDbL];
-  __shared__ int sNb[kDbL];
-  __shared__ int sRt[kDbL + 1];
-  __shared__ int sLive[kDbL + 1];
+  __shared__ int sRt[kDbL + 1];                                  // label counts
+  __shared__ int sPar[kUf ? 2 * kDbL + 4 : (kDbL + 2 + 31) / 32];  // keep bitmap
+  __shared__ int sRaw[kUf ? kDbL : 1];
+  __shared__ int sNb[kUf ? kDbL : 1];
+  __shared__ int sLive[kUf ? kDbL + 1 : 1];
   __shared__ int sN[1];
   const int b = blockIdx.x;
   const size_t base = (size_t)b * c.HW;
   const int M = d.counts[b * kCnt + C_M];
-  if (M <= kDbL) {
-    dbscan_merge<true, kPF>(c, d, base, b, M, sPar, sRaw, sNb, sRt, sLive, sN, sRows);
+  if (M <= kDbRegs) {
+    dbscan_merge_dispatch<kDbRegs>(d, base, b, M, sRows, sRt, (uint32_t*)sPar);
+  } else if (kUf && M <= kDbL) {
+    dbscan_merge_uf<true, kPF>(c, d, base, b, M, sPar, sRaw, sNb, sRt, sLive, sN, sRows);
   } else {  // global scratch: ccl_b (2*HW ints) parent, ccl_a raw, cluster nb, edge_tmp rt, shuf live
-    dbscan_merge<false>(c, d, base, b, M, (int*)(d.ccl_b + base), d.ccl_a + base, d.flat_tmp + base,
-                        d.edge_tmp + base, d.shuf + base, d.shuf + base + c.HW - 1);
+    dbscan_merge_uf<false>(c, d, base, b, M, (int*)(d.ccl_b + base), d.ccl_a + base, d.flat_tmp + base,
+                           d.edge_tmp + base, d.shuf + base, d.shuf + base + c.HW - 1);
   }
 }
 
