@@ -653,9 +653,28 @@ void llsr_icp_destroy(llsr_icp* w);
 const char* llsr_icp_last_error(const llsr_icp* w);
 int32_t llsr_icp_align(llsr_icp* w, const float* d_src4, int32_t n_src, const float* d_tgt4, int32_t n_tgt,
                        const llsr_loop_config* cfg, llsr_icp_result* res, float* d_aligned4, void* hip_stream);
-/* Diagnostic: HIP-event times of the last llsr_icp_align on w, in ms: the correspondence kernels and
- * the solve kernels summed over the iterations, and the whole call's device time. */
+/* P alignments in one set of launches (DESIGN.md §16 "Batch form"). The clouds are concatenated over
+ * the batch as [n][4] float rows: problem p's source is points src_off[p] .. src_off[p + 1] - 1 of
+ * d_src4, its target points tgt_off[p] .. tgt_off[p + 1] - 1 of d_tgt4. The clouds are on the device;
+ * the offsets ([P + 1], in points, non-decreasing) are on the HOST, because the host sizes the
+ * workspace from them. cfgs holds n_cfgs = 1 configuration shared by all problems or n_cfgs = P, one
+ * per problem. res[p], and problem p's rows of d_aligned4 (laid out like d_src4 from src_off[0] on;
+ * may be NULL), are bit for bit what llsr_icp_align gives for that problem alone. A problem that has
+ * finished stays as it is while the others go on; the host reads one word per pass of the loop, and
+ * the call makes at most max(1, largest icp_max_iterations) passes. LLSR_EINVAL: P < 1, decreasing
+ * or negative offsets, n_cfgs not 1 or P, misaligned clouds; LLSR_ERANGE: a problem larger than
+ * LLSR_ICP_MAX_POINTS, or more than 65535 problems. Every problem's grid is sized for the largest
+ * target, so the workspace holds P times that. One call at a time per workspace; synchronises
+ * hip_stream. */
+int32_t llsr_icp_align_batch(llsr_icp* w, int32_t P, const float* d_src4, const int64_t* src_off,
+                             const float* d_tgt4, const int64_t* tgt_off, const llsr_loop_config* cfgs, int32_t n_cfgs,
+                             llsr_icp_result* res, float* d_aligned4, void* hip_stream);
+/* Diagnostic: HIP-event times of the last llsr_icp_align or llsr_icp_align_batch on w, in ms: the
+ * correspondence kernels and the solve kernels summed over the iterations (the batch: over the
+ * passes, all problems together), and the whole call's device time. */
 int32_t llsr_icp_last_times(const llsr_icp* w, float* corr_ms, float* solve_ms, float* total_ms);
+/* Diagnostic: passes of the loop in the last llsr_icp_align_batch on w (0 before the first). */
+int32_t llsr_icp_last_passes(const llsr_icp* w);
 /* One detectLoopClosure + performLoopClosure on the keyframe store. */
 typedef struct llsr_loop_report {
   int32_t found;            /* a candidate exists (0: an empty store or no candidate; nothing else is set) */
@@ -748,6 +767,33 @@ int32_t llsr_mapping_global_map(llsr_handle* h, int32_t b, const llsr_global_map
                                 int64_t cap_planar, llsr_global_map_report* rep, void* hip_stream);
 int32_t llsr_mapping_save_map(llsr_handle* h, int32_t b, float* d_corner, int64_t cap_corner, float* d_surf,
                               int64_t cap_surf, int64_t* n_corner, int64_t* n_surf, void* hip_stream);
+/* Loop closure of the slots (DESIGN.md §16 "Batch form"; the loop-closure thread of the reference,
+ * per slot). llsr_mapping_stage_times arms the next llsr_mapping_batch / _batch_odom call of the same
+ * B with seconds[b] = timeLaserOdometry.seconds() of slot b's scan (host array, copied): the keyframe
+ * that call saves for slot b is stamped with it (MO:1706), and a slot whose MapOptimization runs in
+ * that call keeps it as its `now`. The staging is consumed by that call once its odometry has
+ * advanced (a batch of another B returns LLSR_EINVAL and leaves it staged); a call without staging
+ * leaves its keyframe's time NaN and the slot's `now` as it was. The rollback of a failed
+ * MapOptimization part restores `now`; llsr_mapping_reset clears it and any staging. */
+int32_t llsr_mapping_stage_times(llsr_handle* h, const double* seconds, int32_t B);
+/* llsr_map_keyframe_times of slot b's store. */
+int32_t llsr_mapping_keyframe_times(llsr_handle* h, int32_t b, double* out, int32_t cap);
+/* detectLoopClosure + performLoopClosure of slots 0 .. B - 1 in one call, after the handle's pending
+ * work: per slot the candidate and the submaps on its store (llsr_map_loop_submaps with robot_pos =
+ * the slot's currentRobotPosPoint and now = its staged time; a slot that never got a time holds NaN
+ * and finds no candidate), then ONE llsr_icp_align_batch over the raw clouds of every slot that found
+ * a candidate, on a workspace the handle owns, then per slot the acceptance test and, when accepted,
+ * the constraint. reps[b] is what llsr_map_loop_closure reports for that slot alone (ms: the whole
+ * call's wall time). cfg NULL: llsr_loop_config_lidar of the handle's lidar. Changes no map state;
+ * the aligned and history clouds are not exported. Synchronises hip_stream (NULL: the handle's). */
+int32_t llsr_mapping_loop_closure(llsr_handle* h, const llsr_loop_config* cfg, int32_t B, llsr_loop_report* reps,
+                                  void* hip_stream);
+/* correctPoses (MO:1757-1785) on slot b: llsr_map_set_key_poses on its store, and the same n poses
+ * into the slot's own cloudKeyPoses6D (llsr_mapping_keyposes). latest_estimate6 (may be NULL), in the
+ * layout of transform_aft_mapped, is iSAM2's latestEstimate after the loop factor: transformAftMapped,
+ * transformLast and transformTobeMapped are set to it (MO:1722-1733) and currentRobotPosPoint from it. */
+int32_t llsr_mapping_set_key_poses(llsr_handle* h, int32_t b, const float* poses6, int32_t n,
+                                   const float* latest_estimate6);
 /* Host-only (no device): the pose glue llsr_mapping_batch applies per frame — OdometryToTransform
  * of FA's transformSum (tf2 round trip) into transform_sum, then transformAssociateToMap with the
  * given transformBefMapped / transformAftMapped into transform_tobe_mapped (and transform_incre,

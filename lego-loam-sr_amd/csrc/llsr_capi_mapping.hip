@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -51,9 +52,11 @@ extern "C" int32_t llsr_mapping_reset(llsr_handle* h) {
   for (auto& sl : mp.slot) {
     llsr_map* m = sl.map;
     if (llsr_map_reset(m) != LLSR_OK) return fail(h, LLSR_EINVAL, "llsr_map_reset");
-    sl = llsr_handle::MapSlot{};
+    sl = llsr_handle::MapSlot{};  // (its `now` too: NaN again)
     sl.map = m;
   }
+  mp.times.clear();
+  mp.times_staged = false;
   const int B = (int)mp.slot.size();
   HIP_OK(h, hipMemset(mp.sm.d_deg, 0, sizeof(int) * B));      // isDegenerate = false (MO:285)
   HIP_OK(h, hipMemset(mp.sm.d_matP, 0, sizeof(float) * 36 * B));  // matP zeroed (MO:286)
@@ -68,6 +71,8 @@ void mapping_free(llsr_handle* h) {
   mp.slot.clear();
   if (mp.vg) llsr_map_destroy(mp.vg);
   mp.vg = nullptr;
+  if (mp.icp) llsr_icp_destroy(mp.icp);
+  mp.icp = nullptr;
   mp.sm = llsr_handle::MapSmall{};
   mp.live = false;
 }
@@ -111,8 +116,10 @@ extern "C" int32_t llsr_mapping_init(llsr_handle* h, int32_t mo_mode, const llsr
   return llsr_mapping_reset(h);
 }
 
-// MapOptimization::run for the slots in `step` (their pose glue already applied by the caller).
-static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::vector<char>& step) {
+// MapOptimization::run for the slots in `step` (their pose glue already applied by the caller);
+// times: the staged timeLaserOdometry of the B scans (llsr_mapping_stage_times), or NULL.
+static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::vector<char>& step,
+                          const double* times) {
   auto& mp = h->mp;
   auto& o = h->odo;
   int32_t rc = LLSR_OK;
@@ -280,6 +287,7 @@ static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::v
         (const float*)(mp.ds.p() + dso[NB + 2 * b]), (int32_t)(dso[NB + 2 * b + 1] - dso[NB + 2 * b]),
         (const float*)(mp.ds.p() + dso[NB + 2 * b + 1]), (int32_t)(dso[NB + 2 * b + 2] - dso[NB + 2 * b + 1]), s);
     if (kf < 0) return fail(h, kf, std::string("add_keyframe: ") + llsr_map_last_error(sl.map));
+    if (times) llsr_map_set_keyframe_time(sl.map, kf, times[b]);  // thisPose6D.time (MO:1706)
     sl.keyposes.insert(sl.keyposes.end(), kp, kp + 6);
     sl.mo_frames += 1;
   }
@@ -303,10 +311,17 @@ static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t*
   auto& mp = h->mp;
   if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
   if (B < 1 || B > h->max_batch) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
+  if (mp.times_staged && (int)mp.times.size() != B)
+    return fail(h, LLSR_EINVAL, "the staged scan times (llsr_mapping_stage_times) are for another batch size");
   hipStream_t s;
   HIP_OK(h, enter(h, hip_stream, &s));
   int32_t rc = odo_batch(h, d_xyzi, d_offsets, B, samples, overwrite, s);
   if (rc != LLSR_OK) return rc;
+  // the staged scan times are consumed here, with the odometry's advance
+  std::vector<double> times;
+  const bool timed = mp.times_staged;
+  times.swap(mp.times);
+  mp.times_staged = false;
   auto& o = h->odo;
   HIP_OK(h, hipMemcpyAsync(mp.sm.h_frames, o.frames, sizeof(int) * B, hipMemcpyDeviceToHost, s));
   HIP_OK(h, hipMemcpyAsync(mp.sm.h_tsum, o.tsum, sizeof(float) * 6 * B, hipMemcpyDeviceToHost, s));
@@ -327,7 +342,7 @@ static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t*
     std::memcpy(snap[b].slot.robot, sl.robot, sizeof sl.robot);
     snap[b].slot.mo_frames = sl.mo_frames; snap[b].slot.lm_ran = sl.lm_ran;
     snap[b].slot.n_cq = sl.n_cq; snap[b].slot.n_sq = sl.n_sq; snap[b].slot.cycle = sl.cycle;
-    snap[b].slot.lm = sl.lm; snap[b].slot.mrep = sl.mrep;
+    snap[b].slot.lm = sl.lm; snap[b].slot.mrep = sl.mrep; snap[b].slot.now = sl.now;
     snap[b].n_keyposes = sl.keyposes.size();
     snap[b].n_keyframes = llsr_map_num_keyframes(sl.map);
     snap[b].sel = llsr_mapping::map_selection(sl.map);
@@ -343,6 +358,7 @@ static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t*
       step[b] = 1;
     }
     if (!step[b]) continue;
+    if (timed) sl.now = times[b];  // timeLaserOdometry of the AssociationOut MapOptimization receives
     llsr_mapping::odometry_roundtrip(mp.sm.h_tsum + 6 * b, sl.pose.transformSum);  // OdometryToTransform
     llsr_mapping::transform_associate_to_map(sl.pose);
   }
@@ -352,7 +368,7 @@ static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t*
     HIP_OK(h, hipMemcpyAsync(mp.sm.d_deg_bak, mp.sm.d_deg, sizeof(int) * o.B, hipMemcpyDeviceToDevice, s));
     HIP_OK(h, hipMemcpyAsync(mp.sm.d_matP_bak, mp.sm.d_matP, sizeof(float) * 36 * o.B, hipMemcpyDeviceToDevice, s));
   }
-  rc = any ? mapping_mo(h, B, s, step) : LLSR_OK;
+  rc = any ? mapping_mo(h, B, s, step, timed ? times.data() : nullptr) : LLSR_OK;
   if (rc != LLSR_OK) {
     const std::string msg = h->err;
     (void)hipStreamSynchronize(s);
@@ -362,7 +378,7 @@ static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t*
       sl.pose = sn.pose;
       std::memcpy(sl.robot, sn.robot, sizeof sl.robot);
       sl.mo_frames = sn.mo_frames; sl.lm_ran = sn.lm_ran; sl.n_cq = sn.n_cq; sl.n_sq = sn.n_sq;
-      sl.cycle = sn.cycle; sl.lm = sn.lm; sl.mrep = sn.mrep;
+      sl.cycle = sn.cycle; sl.lm = sn.lm; sl.mrep = sn.mrep; sl.now = sn.now;
       sl.keyposes.resize(snap[b].n_keyposes);
       llsr_mapping::truncate_keyframes(sl.map, snap[b].n_keyframes);
       llsr_mapping::set_map_selection(sl.map, snap[b].sel);
@@ -462,4 +478,112 @@ extern "C" int32_t llsr_mapping_keyposes(llsr_handle* h, int32_t b, float* out, 
   const int n = (int)(kp.size() / 6);
   if (out && cap > 0) std::memcpy(out, kp.data(), sizeof(float) * 6 * (size_t)(n < cap ? n : cap));
   return n;
+}
+
+// ---- loop closure of the slots (detectLoopClosure / performLoopClosure / correctPoses per slot) ----
+extern "C" int32_t llsr_mapping_stage_times(llsr_handle* h, const double* seconds, int32_t B) {
+  if (!h) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (!seconds) return fail(h, LLSR_EINVAL, "llsr_mapping_stage_times: seconds is NULL");
+  if (B < 1 || B > h->max_batch) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
+  mp.times.assign(seconds, seconds + B);
+  mp.times_staged = true;
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_mapping_keyframe_times(llsr_handle* h, int32_t b, double* out, int32_t cap) {
+  if (!h) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (b < 0 || b >= (int)mp.slot.size()) return fail(h, LLSR_ERANGE, "slot outside [0, max_batch)");
+  const int32_t n = llsr_map_keyframe_times(mp.slot[b].map, out, cap);
+  return n >= 0 ? n : fail(h, n, "llsr_mapping_keyframe_times: bad arguments");
+}
+
+extern "C" int32_t llsr_mapping_loop_closure(llsr_handle* h, const llsr_loop_config* cfg, int32_t B,
+                                             llsr_loop_report* reps, void* hip_stream) {
+  if (!h || !reps) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (B < 1 || B > (int)mp.slot.size()) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
+  llsr_loop_config own;
+  if (!cfg) {  // the block of the handle's lidar, chosen as llsr_mapping_init chooses the map's
+    llsr_loop_config_lidar(&own, h->cfg.use_vlp32c ? LLSR_LIDAR_VLP32C : h->dc.H == 64 ? LLSR_LIDAR_HDL64E
+                                                                                          : LLSR_LIDAR_VLP16);
+    cfg = &own;
+  }
+  if (cfg->search_num < 0 || !(cfg->leaf > 0)) return fail(h, LLSR_EINVAL, "loop closure: bad configuration");
+  const auto t0 = std::chrono::steady_clock::now();
+  hipStream_t s;
+  HIP_OK(h, enter(h, hip_stream, &s));
+  HIP_OK(h, sync_handle_streams(h));
+  // §16 steps 1-5 per slot, each in its store's own scratch (they stay valid: one store per slot)
+  std::vector<const float4*> src(B, nullptr), tgt(B, nullptr);
+  std::vector<int> found;
+  std::vector<int64_t> soff(1, 0), toff(1, 0);
+  for (int b = 0; b < B; ++b) {
+    auto& sl = mp.slot[b];
+    const int32_t rc = llsr_mapping::loop_submaps_raw(sl.map, cfg, sl.robot, sl.now, &reps[b], &src[b], &tgt[b], s);
+    if (rc != LLSR_OK) return fail(h, rc, std::string("loop closure: ") + llsr_map_last_error(sl.map));
+    if (!reps[b].found) continue;
+    if (reps[b].n_source > LLSR_ICP_MAX_POINTS || reps[b].n_target > LLSR_ICP_MAX_POINTS)
+      return fail(h, LLSR_ERANGE, "loop closure: more than LLSR_ICP_MAX_POINTS points to align");
+    found.push_back(b);
+    soff.push_back(soff.back() + reps[b].n_source);
+    toff.push_back(toff.back() + reps[b].n_target);
+  }
+  const int P = (int)found.size();
+  if (P > 0) {
+    // MO:1011-1012: the raw clouds, not the downsampled ones, gathered in the batch's layout
+    int32_t rc = mp_grow(h, mp.lsrc, (size_t)soff[P] + 1, 0, s);
+    if (rc == LLSR_OK) rc = mp_grow(h, mp.ltgt, (size_t)toff[P] + 1, 0, s);
+    if (rc != LLSR_OK) return rc;
+    for (int i = 0; i < P; ++i) {
+      const int b = found[i];
+      if (reps[b].n_source > 0)
+        HIP_OK(h, hipMemcpyAsync(mp.lsrc.p() + soff[i], src[b], (size_t)reps[b].n_source * sizeof(float4),
+                                 hipMemcpyDeviceToDevice, s));
+      if (reps[b].n_target > 0)
+        HIP_OK(h, hipMemcpyAsync(mp.ltgt.p() + toff[i], tgt[b], (size_t)reps[b].n_target * sizeof(float4),
+                                 hipMemcpyDeviceToDevice, s));
+    }
+    if (!mp.icp) mp.icp = llsr_icp_create(h->device);
+    if (!mp.icp) return fail(h, LLSR_ENOMEM, "loop closure: no ICP workspace");
+    std::vector<llsr_icp_result> res(P);
+    rc = llsr_icp_align_batch(mp.icp, P, (const float*)mp.lsrc.p(), soff.data(), (const float*)mp.ltgt.p(), toff.data(),
+                              cfg, 1, res.data(), nullptr, s);
+    if (rc != LLSR_OK) return fail(h, rc, std::string("loop closure: ") + llsr_icp_last_error(mp.icp));
+    for (int i = 0; i < P; ++i) {
+      llsr_loop_report& rep = reps[found[i]];
+      const auto& kp = mp.slot[found[i]].keyposes;
+      rep.icp = res[i];
+      rep.accepted = rep.icp.converged && !(rep.icp.fitness > (double)cfg->fitness_score);  // MO:1038-1040
+      if (rep.accepted)
+        llsr_loop_constraint(rep.icp.T, kp.data() + 6 * (size_t)rep.latest_id, kp.data() + 6 * (size_t)rep.closest_id,
+                             rep.icp.fitness, rep.pose_from, rep.pose_to, &rep.variance);
+    }
+  }
+  const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (int b = 0; b < B; ++b)
+    if (reps[b].found) reps[b].ms = ms;
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_mapping_set_key_poses(llsr_handle* h, int32_t b, const float* poses6, int32_t n,
+                                              const float* latest_estimate6) {
+  if (!h) return LLSR_EINVAL;
+  llsr_handle::MapSlot* sl = nullptr;
+  int32_t rc = mapping_slot_map(h, b, &sl);
+  if (rc != LLSR_OK) return rc;
+  rc = llsr_map_set_key_poses(sl->map, poses6, n);  // validates poses6 / n against the store
+  if (rc != LLSR_OK) return fail(h, rc, std::string("set key poses: ") + llsr_map_last_error(sl->map));
+  if (n > 0) std::memcpy(sl->keyposes.data(), poses6, sizeof(float) * 6 * (size_t)n);
+  if (latest_estimate6) {  // MO:1722-1733 with iSAM2's latestEstimate after the loop factor
+    auto& P = sl->pose;
+    for (int k = 0; k < 6; ++k)
+      P.transformAftMapped[k] = P.transformLast[k] = P.transformTobeMapped[k] = latest_estimate6[k];
+    for (int k = 0; k < 3; ++k) sl->robot[k] = P.transformAftMapped[3 + k];
+  }
+  return LLSR_OK;
 }

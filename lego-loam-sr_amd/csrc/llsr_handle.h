@@ -146,6 +146,7 @@ struct LLSR_HIDDEN llsr_handle {
     llsr_lm_report lm{};
     llsr_map_report mrep{};
     std::vector<float> keyposes;       // [keyframes][6]
+    double now = NAN;                  // timeLaserOdometry.seconds() of the last staged scan MapOptimization ran
   };
   // device: pose [B][6], report [B], deg [B], matP [B][36], off [5][B+1], and the deg / matP of
   // the frame before (rollback); pinned host mirror
@@ -166,6 +167,13 @@ struct LLSR_HIDDEN llsr_handle {
     std::vector<MapSlot> slot;
     GrowBuf outl, ds, tot, cmap;       // cmap: empty-map base
     MapSmall sm;
+    // loop closure of the slots (llsr_mapping_stage_times / llsr_mapping_loop_closure): the scan times
+    // staged for the next batch call, the gathered raw clouds of the slots with a candidate, and the
+    // chain's own ICP workspace (created on first use)
+    std::vector<double> times;
+    bool times_staged = false;
+    GrowBuf lsrc, ltgt;
+    llsr_icp* icp = nullptr;
   } mp;
   // IMU de-skew (llsr_stage_imu): device windows + per-slot carry and their pinned staging, allocated
   // on the first staging call; `armed` until a batch's feature stage consumes it

@@ -646,6 +646,174 @@ inline void icp_run_host(const IcpArgs& a) {
   fitsum_body(a);
 }
 
+// ---- the batch form (DESIGN.md §16 "Batch form"): P alignments in one set of launches --------------
+// Problem p has its own IcpArgs in a table; a batch kernel finds its problem from blockIdx.y and
+// calls the body above on that entry, so a problem's sums, ties, stop rule and fitness are the single
+// call's. What the batch adds is below: which blocks of a launch sized for the largest problem belong
+// to a problem, which problems still take part in the loop, and where problem p's slices of the shared
+// buffers lie.
+
+// a block past the problem's own extent returns at once
+LLSR_HD bool batch_block(int block, int n, int block_size) { return block < blocks_for(n, block_size); }
+// a problem whose state has left kStateNone takes no further part in the loop kernels: its state,
+// final and working cloud stay as the pass that finished it left them
+LLSR_HD bool batch_live(const IcpArgs& a) { return a.st->state == kStateNone; }
+// k_icp_init_b, one lane per problem
+LLSR_HD void init_body(const IcpArgs& a) {
+  state_init(a.st);
+  a.box[0] = a.box[1] = a.box[2] = kBoxEmptyLo;
+  a.box[3] = a.box[4] = a.box[5] = kBoxEmptyHi;
+}
+// k_icp_finish_b, one lane per problem: true when this pass ended the problem's loop (the caller
+// takes it off the count of unfinished problems, an integer atomic on the device)
+LLSR_HD bool finish_batch_body(const IcpArgs& a) {
+  if (!batch_live(a)) return false;
+  finish_body(a);
+  return !batch_live(a);
+}
+
+// Launch extents of a batch: each sized for the largest problem
+struct IcpBatchDims {
+  int box_blocks, corr_blocks, sigma_blocks;
+  int max_passes;  // max(1, largest max_iterations): the stop rule ends every problem by then
+};
+inline IcpBatchDims icp_batch_dims(const IcpArgs* tab, int P) {
+  int ns = 0, nt = 0, it = 1;
+  for (int p = 0; p < P; ++p) {
+    if (tab[p].n_src > ns) ns = tab[p].n_src;
+    if (tab[p].n_tgt > nt) nt = tab[p].n_tgt;
+    if (tab[p].max_iterations > it) it = tab[p].max_iterations;
+  }
+  return {blocks_for(nt, kCorrBlock), blocks_for(ns, kCorrBlock), blocks_for(9 * sigma_blocks_max(ns), kCorrBlock), it};
+}
+
+// Element counts of the shared buffers of a batch and problem p's slices of them. The per-point
+// buffers are laid out like the concatenated source (problem p at point src_off[p] - src_off[0]) with
+// one point more at the end, so an empty problem's slice is still a live address; every problem's
+// grid has the table size and the capacity of the largest target.
+struct IcpBatchLayout {
+  int P = 0, log2T = 0, cap = 0;         // cap = the largest target, log2T = grid_log2_table(cap)
+  size_t tab = 0, cells = 0, points = 0, part = 0;  // slots, target points, source points, floats of `part`
+};
+inline IcpBatchLayout icp_batch_layout(int P, const int64_t* src_off, const int64_t* tgt_off) {
+  IcpBatchLayout L;
+  L.P = P;
+  for (int p = 0; p < P; ++p) {
+    const int nt = (int)(tgt_off[p + 1] - tgt_off[p]);
+    if (nt > L.cap) L.cap = nt;
+    L.part += 9 * (size_t)sigma_blocks_max((int)(src_off[p + 1] - src_off[p]));
+  }
+  L.log2T = llsr::grid_log2_table(L.cap);
+  L.tab = (size_t)P << L.log2T;
+  L.cells = (size_t)P * (size_t)(L.cap > 0 ? L.cap : 1);
+  L.points = (size_t)(src_off[P] - src_off[0]) + 1;
+  return L;
+}
+// The base pointers of the shared buffers (sizes in elements, from the layout)
+struct IcpBatchBuffers {
+  const float* src4;      // the concatenated sources from point src_off[0] on (unused when all are empty)
+  const float* tgt4;      // the same for the targets
+  llsr::CellSlot* tab;    // [L.tab]
+  float* cells4;          // [L.cells][4]
+  int* box;               // [6 P]
+  float *work4, *ps4, *pd4;  // [L.points][4]
+  int* match;             // [L.points]
+  float* d2;              // [L.points]
+  float* part;            // [L.part]
+  IcpState* st;           // [P]
+  float* aligned4;        // [L.points][4]; the working cloud serves when the caller wants no aligned cloud
+};
+// Fill entry p of the table (the parameters max_iterations, eps_*, mcd2 are the caller's); part_at is
+// the running offset into `part`, advanced by the problem's share
+inline void icp_batch_entry(const IcpBatchLayout& L, const IcpBatchBuffers& b, const int64_t* src_off,
+                            const int64_t* tgt_off, int p, size_t* part_at, IcpArgs* a) {
+  const size_t so = (size_t)(src_off[p] - src_off[0]), to = (size_t)(tgt_off[p] - tgt_off[0]);
+  a->n_src = (int32_t)(src_off[p + 1] - src_off[p]);
+  a->n_tgt = (int32_t)(tgt_off[p + 1] - tgt_off[p]);
+  a->log2T = L.log2T;
+  a->tab = b.tab + ((size_t)p << L.log2T);
+  a->cells4 = b.cells4 + 4 * (size_t)p * (size_t)L.cap;
+  a->box = b.box + 6 * (size_t)p;
+  a->work4 = b.work4 + 4 * so;
+  // an empty cloud is given the problem's own slice of the workspace, never a null or outside pointer
+  a->src4 = a->n_src > 0 ? b.src4 + 4 * so : a->work4;
+  a->tgt4 = a->n_tgt > 0 ? b.tgt4 + 4 * to : a->cells4;
+  a->match = b.match + so;
+  a->d2 = b.d2 + so;
+  a->ps4 = b.ps4 + 4 * so;
+  a->pd4 = b.pd4 + 4 * so;
+  a->part = b.part + *part_at;
+  *part_at += 9 * (size_t)sigma_blocks_max(a->n_src);
+  a->st = b.st + p;
+  a->aligned4 = b.aligned4 + 4 * so;
+}
+
+// The batch launches of llsr_icp_align_batch as loops over their (block.x, block.y, thread) ranges,
+// over a table whose grids were built with grid_build_host at the batch's log2T. Returns the number
+// of passes of the loop, or -1 when a problem is still unfinished after max_passes (which the stop
+// rule excludes).
+inline int icp_run_batch_host(const IcpArgs* tab, int P) {
+  const IcpBatchDims dims = icp_batch_dims(tab, P);
+  int live = P;
+  for (int p = 0; p < P; ++p) init_body(tab[p]);
+  for (int p = 0; p < P; ++p)
+    for (int blk = 0; blk < dims.box_blocks; ++blk) {
+      const IcpArgs& a = tab[p];
+      if (!batch_block(blk, a.n_tgt, kCorrBlock)) continue;
+      for (int t = 0; t < kCorrBlock; ++t) {
+        int c[3];
+        if (!box_cell(a, point_of(blk, t, kCorrBlock), c)) continue;
+        for (int k = 0; k < 3; ++k) {
+          if (c[k] < a.box[k]) a.box[k] = c[k];
+          if (c[k] > a.box[3 + k]) a.box[3 + k] = c[k];
+        }
+      }
+    }
+  for (int p = 0; p < P; ++p)
+    for (size_t k = 0; k < 4 * (size_t)tab[p].n_src; ++k) tab[p].work4[k] = tab[p].src4[k];
+  int passes = 0;
+  while (live > 0) {
+    if (passes >= dims.max_passes) return -1;
+    ++passes;
+    for (int p = 0; p < P; ++p)
+      for (int blk = 0; blk < dims.corr_blocks; ++blk) {
+        const IcpArgs& a = tab[p];
+        if (!batch_live(a) || !batch_block(blk, a.n_src, kCorrBlock)) continue;
+        for (int t = 0; t < kCorrBlock; ++t) corr_body(a, point_of(blk, t, kCorrBlock));
+      }
+    for (int p = 0; p < P; ++p) {
+      const IcpArgs& a = tab[p];
+      if (!batch_live(a)) continue;
+      int pos = 0;  // the scan of k_icp_pack_b, serially
+      for (int tile = 0; tile < blocks_for(a.n_src, kPackBlock); ++tile)
+        for (int t = 0; t < kPackBlock; ++t) {
+          const int i = point_of(tile, t, kPackBlock);
+          if (pack_keep(a, i)) pack_write(a, i, pos++);
+        }
+      a.st->n_pairs = pos;
+    }
+    for (int p = 0; p < P; ++p)
+      if (batch_live(tab[p]))
+        for (int lane = 0; lane < kLaneBlock; ++lane) means_body(tab[p], lane);
+    for (int p = 0; p < P; ++p)
+      for (int blk = 0; blk < dims.sigma_blocks; ++blk) {
+        const IcpArgs& a = tab[p];
+        if (!batch_live(a) || !batch_block(blk, 9 * sigma_blocks_max(a.n_src), kCorrBlock)) continue;
+        for (int t = 0; t < kCorrBlock; ++t) sigma_body(a, point_of(blk, t, kCorrBlock));
+      }
+    for (int p = 0; p < P; ++p)
+      if (finish_batch_body(tab[p])) --live;
+  }
+  for (int p = 0; p < P; ++p)
+    for (int blk = 0; blk < dims.corr_blocks; ++blk) {
+      const IcpArgs& a = tab[p];
+      if (!batch_block(blk, a.n_src, kCorrBlock)) continue;
+      for (int t = 0; t < kCorrBlock; ++t) fit_body(a, point_of(blk, t, kCorrBlock));
+    }
+  for (int p = 0; p < P; ++p) fitsum_body(tab[p]);
+  return passes;
+}
+
 // pcl::getTransformation(x, y, z, roll, pitch, yaw) as a row-major 3x4 (glibc float libm)
 inline void get_transformation(float x, float y, float z, float roll, float pitch, float yaw, float* t) {
   const float A = cosf(yaw), B = sinf(yaw), C = cosf(pitch), D = sinf(pitch), E = cosf(roll), F = sinf(roll);

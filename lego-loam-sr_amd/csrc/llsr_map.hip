@@ -1387,6 +1387,18 @@ void loop_report_clear(llsr_loop_report* rep) {
 
 }  // namespace
 
+int32_t llsr_mapping::loop_submaps_raw(llsr_map* m, const llsr_loop_config* cfg, const float* robot_pos, double now,
+                                       llsr_loop_report* rep, const float4** source, const float4** target,
+                                       hipStream_t s) {
+  loop_report_clear(rep);
+  MAP_OK(m, hipSetDevice(m->device));
+  LoopClouds lc;
+  const int32_t rc = loop_submaps_scratch(m, cfg, robot_pos, now, rep, &lc, s);
+  *source = lc.source;
+  *target = lc.target;
+  return rc;
+}
+
 extern "C" int32_t llsr_map_loop_submaps(llsr_map* m, const llsr_loop_config* cfg, const float robot_pos[3], double now,
                                          llsr_loop_report* rep, float* d_source, int64_t cap_source, float* d_target,
                                          int64_t cap_target, float* d_source_ds, int64_t cap_sds, float* d_target_ds,

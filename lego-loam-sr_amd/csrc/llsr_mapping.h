@@ -43,6 +43,11 @@ int32_t voxel_multi(llsr_map* m, const float4* const* src, const long long* n, c
 // empty maps (the caller skips the call for it, MO:1097). Synchronises s.
 int32_t extract_multi(llsr_map* eng, llsr_map* const* maps, int n, const float* pos, llsr_map_report* reps,
                       const float4** out, long long* off_c, long long* off_s, hipStream_t s);
+// The loop closure's candidate and submaps (as llsr_map_loop_submaps) left in
+// m's own scratch: rep as that call reports it, *source / *target the raw clouds (rep->n_source /
+// n_target points, valid until m's next call; null without a candidate). Synchronises s.
+int32_t loop_submaps_raw(llsr_map* m, const llsr_loop_config* cfg, const float* robot_pos, double now,
+                         llsr_loop_report* rep, const float4** source, const float4** target, hipStream_t s);
 // Drop keyframes from index `keep` on (a failed frame's keyframe, llsr_mapping_batch rollback).
 void truncate_keyframes(llsr_map* m, int keep);
 

@@ -52,6 +52,8 @@ EXPORTS = [
     "llsr_map_set_key_poses", "llsr_loop_candidate", "llsr_umeyama3", "llsr_loop_constraint",
     "llsr_icp_align_host", "llsr_icp_create", "llsr_icp_destroy", "llsr_icp_last_error", "llsr_icp_align",
     "llsr_icp_last_times", "llsr_map_loop_submaps", "llsr_map_loop_closure",
+    "llsr_icp_align_batch", "llsr_icp_last_passes", "llsr_mapping_stage_times", "llsr_mapping_keyframe_times",
+    "llsr_mapping_loop_closure", "llsr_mapping_set_key_poses",
     "llsr_imu_init", "llsr_imu_callback", "llsr_imu_scan_window", "llsr_imu_deskew_host", "llsr_stage_imu",
     "llsr_fetch_imu_report", "llsr_set_imu_undistortion", "llsr_integrate_transformation_imu",
     "llsr_transform_to_end_imu", "llsr_first_scan_imu",
@@ -186,6 +188,14 @@ def lib():
         L.llsr_icp_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(_abi.LoopConfig),
                                      C.POINTER(_abi.IcpResult), C.c_void_p, C.c_void_p]
         L.llsr_icp_last_times.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 3
+        L.llsr_icp_align_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llsr_icp_last_passes.argtypes = [C.c_void_p]
+        L.llsr_mapping_stage_times.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.llsr_mapping_keyframe_times.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.llsr_mapping_loop_closure.argtypes = [C.c_void_p, C.POINTER(_abi.LoopConfig), C.c_int32, C.c_void_p,
+                                                C.c_void_p]
+        L.llsr_mapping_set_key_poses.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         _loop = [C.POINTER(_abi.LoopConfig), C.c_void_p, C.c_double, C.POINTER(_abi.LoopReport)]
         L.llsr_map_loop_submaps.argtypes = [C.c_void_p] + _loop + [C.c_void_p, C.c_int64] * 4 + [C.c_void_p]
         L.llsr_map_loop_closure.argtypes = [C.c_void_p, C.c_void_p] + _loop + [C.c_void_p, C.c_int64] * 2 + [C.c_void_p]
@@ -561,6 +571,38 @@ class Pipeline:
         rc, c, su = _save_map(torch, torch.device("cuda", self.device), call)
         self._check(rc, "llsr_mapping_save_map")
         return c, su
+
+    def mapping_stage_times(self, seconds):
+        """timeLaserOdometry.seconds() of each slot's scan in the next mapping_batch / _batch_odom call
+        (llsr_mapping_stage_times): stamps the keyframes that call saves."""
+        t = np.ascontiguousarray(seconds, np.float64).reshape(-1)
+        self._check(lib().llsr_mapping_stage_times(self._h, t.ctypes.data, len(t)), "llsr_mapping_stage_times")
+
+    def mapping_keyframe_times(self, b: int) -> np.ndarray:
+        """cloudKeyPoses6D[*].time of slot b (llsr_mapping_keyframe_times): NaN where none was staged."""
+        n = lib().llsr_mapping_keyframe_times(self._h, b, None, 0)
+        if n < 0:
+            self._check(n, "llsr_mapping_keyframe_times")
+        out = np.zeros(max(n, 1), np.float64)
+        lib().llsr_mapping_keyframe_times(self._h, b, out.ctypes.data, n)
+        return out[:n].copy()
+
+    def mapping_loop_closure(self, B: int, cfg: _abi.LoopConfig | None = None, stream: int = 0) -> list:
+        """detectLoopClosure + performLoopClosure of slots 0 .. B - 1 with one batched alignment
+        (llsr_mapping_loop_closure): one llsr_loop_report dict per slot."""
+        reps = (_abi.LoopReport * B)()
+        self._check(lib().llsr_mapping_loop_closure(self._h, C.byref(cfg) if cfg is not None else None, B, reps,
+                                                    C.c_void_p(stream)), "llsr_mapping_loop_closure")
+        return [r.as_dict() for r in reps]
+
+    def mapping_set_key_poses(self, b: int, poses6, latest_estimate=None):
+        """correctPoses on slot b (llsr_mapping_set_key_poses): the first len(poses6) key poses (x, y, z,
+        roll, pitch, yaw) and, when given, iSAM2's latestEstimate in transform_aft_mapped's layout."""
+        p = np.ascontiguousarray(poses6, np.float32).reshape(-1, 6)
+        e = None if latest_estimate is None else np.ascontiguousarray(latest_estimate, np.float32).reshape(6)
+        self._check(lib().llsr_mapping_set_key_poses(self._h, b, p.ctypes.data, len(p),
+                                                     None if e is None else e.ctypes.data),
+                    "llsr_mapping_set_key_poses")
 
 
 def mapping_associate(transform_sum_fa, bef, aft):
@@ -1011,8 +1053,52 @@ class Icp:
         r["aligned"] = out[:a.shape[0]]
         return r
 
+    def align_batch(self, srcs, tgts, cfgs=None) -> list:
+        """llsr_icp_align_batch: srcs[p] onto tgts[p] for every p in one set of launches. cfgs is None
+        (the default block), one LoopConfig for all problems, or a list with one per problem. Returns
+        one dict per problem: the llsr_icp_result fields and "aligned" (a view of one device tensor)."""
+        torch = self._torch
+        P = len(srcs)
+        if P < 1 or len(tgts) != P:
+            raise ValueError("one target per source, at least one problem")
+
+        def cat(clouds):
+            host = [np.asarray(c.cpu() if hasattr(c, "cpu") else c, np.float32).reshape(-1, 4) for c in clouds]
+            off = np.zeros(P + 1, np.int64)
+            off[1:] = np.cumsum([len(c) for c in host])
+            dev = torch.from_numpy(np.concatenate(host + [np.zeros((1, 4), np.float32)])).to(self.device)
+            return dev, off
+
+        (a, so), (b, to) = cat(srcs), cat(tgts)
+        out = torch.empty_like(a)
+        if cfgs is None or isinstance(cfgs, _abi.LoopConfig):
+            arr = (_abi.LoopConfig * 1)(cfgs if cfgs is not None else loop_config())
+        else:
+            if len(cfgs) != P:
+                raise ValueError("one configuration, or one per problem")
+            arr = (_abi.LoopConfig * P)(*cfgs)
+        res = (_abi.IcpResult * P)()
+        self._s.wait_stream(torch.cuda.current_stream(self.device))
+        rc = lib().llsr_icp_align_batch(self._w, P, C.c_void_p(a.data_ptr()), so.ctypes.data, C.c_void_p(b.data_ptr()),
+                                        to.ctypes.data, arr, len(arr), res, C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(self._s.cuda_stream))
+        if rc != 0:
+            raise LlsrError(f"llsr_icp_align_batch failed ({rc}): {lib().llsr_icp_last_error(self._w).decode()}")
+        torch.cuda.current_stream(self.device).wait_stream(self._s)
+        rs = []
+        for p in range(P):
+            r = res[p].as_dict()
+            r["aligned"] = out[so[p]:so[p + 1]]
+            rs.append(r)
+        return rs
+
+    def last_passes(self) -> int:
+        """Passes of the loop in the last align_batch (llsr_icp_last_passes)."""
+        return lib().llsr_icp_last_passes(self._w)
+
     def last_times(self) -> dict:
-        """HIP-event ms of the last align: the correspondence and solve kernels summed, the whole call."""
+        """HIP-event ms of the last align or align_batch: the correspondence and solve kernels summed, the
+        whole call."""
         c, v, t = C.c_float(), C.c_float(), C.c_float()
         lib().llsr_icp_last_times(self._w, C.byref(c), C.byref(v), C.byref(t))
         return {"corr_ms": c.value, "solve_ms": v.value, "total_ms": t.value}
