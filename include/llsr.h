@@ -581,7 +581,8 @@ int32_t llsr_keypose_radius_sorted(const float* poses4, int32_t K, const float p
  * the device (llsr_icp_align) and on the host (llsr_icp_align_host), the acceptance test, the pose
  * constraint, and the corrected poses coming back. llsr_map_loop_closure runs all of it in one call;
  * the pieces are entry points of their own. DESIGN.md §16 is the specification of the whole path (PCL
- * and Eigen are restated, not linked). The BetweenFactor and iSAM2 stay in the node. */
+ * and Eigen are restated, not linked). The BetweenFactor and iSAM2 stay in the node, or the llsr_pg_*
+ * calls below take their place. */
 typedef struct llsr_loop_config {
   float search_radius;     /* history_keyframe_search_radius (CFG:29 / 97 / 165) */
   int32_t search_num;      /* history_keyframe_search_num (CFG:30 / 98 / 166) */
@@ -794,6 +795,90 @@ int32_t llsr_mapping_loop_closure(llsr_handle* h, const llsr_loop_config* cfg, i
  * transformLast and transformTobeMapped are set to it (MO:1722-1733) and currentRobotPosPoint from it. */
 int32_t llsr_mapping_set_key_poses(llsr_handle* h, int32_t b, const float* poses6, int32_t n,
                                    const float* latest_estimate6);
+/* ---- Pose graph: the factor graph of MO:1086-1090 / 1612-1690, batched ----
+ * P independent graphs in one object: per graph K poses, a prior on pose 0, K - 1 odometry factors and
+ * the loop factors in insertion order; llsr_pg_optimize runs a Gauss-Newton in double over every
+ * graph that received a loop factor since its last optimisation, all of them in one set of launches
+ * per pass. GTSAM is restated, not linked; §19 marks the choices. Poses are the store's floats (x, y,
+ * z, roll, pitch, yaw: llsr_mapping_keyposes, llsr_map_set_key_poses); a loop factor takes
+ * llsr_loop_constraint's outputs as they are. A node that keeps GTSAM ignores these calls.
+ * hip_device == LLSR_PG_HOST: no device; the same loop bodies run serially over heap buffers of the
+ * device workspace's sizes, and every result is bit for bit the device's. */
+#define LLSR_PG_HOST (-1)
+typedef struct llsr_pg llsr_pg;
+typedef struct llsr_pg_config {
+  int32_t max_iterations;      /* 100 (NonlinearOptimizerParams) */
+  int32_t pad;
+  double relative_error_tol;   /* 1e-5 */
+  double absolute_error_tol;   /* 1e-5 */
+} llsr_pg_config;
+/* state: 0 clean (no loop factor since the last optimisation: skipped, nothing else set but poses /
+ * loops), 1 stopped by the absolute tolerance, 2 by the relative tolerance, 3 by max_iterations, 4 the
+ * error rose (the iterate before is kept; `iterations` counts the step taken back), 5 failed (a pivot
+ * of the factorisation was not finite and positive; the poses stay at the iterate it was reached
+ * with). error_before / error_after: half the sum of squared whitened residuals at the start and at
+ * the iterate kept. */
+typedef struct llsr_pg_report {
+  int32_t state;
+  int32_t iterations;
+  double error_before;
+  double error_after;
+  int32_t poses;
+  int32_t loops;
+  float ms;          /* the whole call (HIP events on a device, wall time on the host), all graphs */
+  int32_t moved;     /* the estimate differs from the one before the call (a step was kept) */
+} llsr_pg_report;
+/* Capacities are per graph: poses, loop factors, 6x6 blocks of the normal equations' row envelope (a
+ * graph needs 2 K - 1 blocks plus max(from, to) - min(from, to) - 1 for the longest loop ending on
+ * each row). NULL: P < 1 or P > 65535, a capacity < 1 (max_loops < 0), no such device, no memory. */
+llsr_pg* llsr_pg_create(int32_t hip_device, int32_t P, int32_t max_poses, int32_t max_loops,
+                        int64_t max_envelope_blocks);
+void llsr_pg_destroy(llsr_pg* g);
+const char* llsr_pg_last_error(const llsr_pg* g);
+int32_t llsr_pg_config_default(llsr_pg_config* cfg);
+/* Empty graph p (-1: all). */
+int32_t llsr_pg_reset(llsr_pg* g, int32_t p);
+/* Append n keyframes to graph p: pose 0 gets the prior at its own value, keyframe k the odometry
+ * factor between(estimate of k - 1 now, poses6[k]) (MO:1641-1664). Never optimises: the new factor has
+ * no error at the new pose, and the estimate of the others stays. */
+int32_t llsr_pg_append(llsr_pg* g, int32_t p, const float* poses6, int32_t n);
+/* The loop factor of MO:1086-1088 between from_id (latest) and to_id (closest):
+ * pose_from.between(pose_to) of llsr_loop_constraint's outputs, one variance for all six components. */
+int32_t llsr_pg_add_loop(llsr_pg* g, int32_t p, int32_t from_id, int32_t to_id, const float pose_from6[6],
+                         const float pose_to6[6], float variance);
+/* Optimise every graph with a loop factor since its last optimisation; reps[P] (may be NULL). cfg NULL:
+ * the defaults. Synchronises hip_stream (NULL: the object's own; ignored on the host). */
+int32_t llsr_pg_optimize(llsr_pg* g, const llsr_pg_config* cfg, llsr_pg_report* reps, void* hip_stream);
+/* Graph p's estimate, x, y, z, roll, pitch, yaw per pose into out6[6 * cap]; returns K (may exceed
+ * cap). A pose no optimisation moved is the appended floats bit for bit. */
+int32_t llsr_pg_poses(const llsr_pg* g, int32_t p, float* out6, int32_t cap);
+/* LLSR_EINVAL: ids out of range, from_id == to_id, a variance that is not finite and positive, a pose
+ * that is not finite, a problem index outside [0, P); LLSR_ERANGE: the pose, loop or envelope capacity
+ * is exceeded. A refused call leaves the graph unchanged.
+ *
+ * The mapping chain's graphs, opt-in: after llsr_mapping_enable_pose_graph(h, 1, max_loops) every
+ * keyframe a slot saves is appended to the slot's graph (inside the rollback of a failed
+ * MapOptimization part), llsr_mapping_reset empties the graphs, and llsr_mapping_close_loops runs
+ * llsr_mapping_loop_closure, adds the loop factor of every accepted slot, runs ONE llsr_pg_optimize
+ * over all slots and, for every slot whose graph moved, llsr_mapping_set_key_poses with the new poses
+ * and the newest pose as latest_estimate6 (MO:1722-1733). A slot without an accepted loop is
+ * untouched. Enabling starts the graphs from the slots' current key poses; on == 0 drops them.
+ * pg_reps[B] may be NULL. The graphs live on the handle's device.
+ * When llsr_mapping_close_loops fails after the loop closure itself (a graph's loop capacity is full,
+ * the optimisation fails), the loop factors it already added stay in their graphs and no key pose has
+ * changed: those graphs are optimised, with whatever is added then, by the next call. The graphs
+ * follow the slots only through these calls: key poses set from outside (llsr_mapping_set_key_poses)
+ * do not reach a slot's graph, so a caller that corrects poses itself should not enable them, or
+ * should enable them again afterwards (which starts the graphs from the key poses as they are then).
+ * Memory: one object holds all max_batch graphs at the capacity of the fullest, K poses (256 at
+ * first, doubled when a slot fills it) and E envelope blocks (4 K at first, at most (2 + max_loops) K)
+ * each: about 264 K + 776 (K + max_loops) + 288 E bytes per slot on the device, 0.6 MB at first for
+ * max_loops = 64 (0.6 GB for 1024 slots), and about 250 K + 144 (K + max_loops) on the host (0.1 MB). */
+int32_t llsr_mapping_enable_pose_graph(llsr_handle* h, int32_t on, int32_t max_loops);
+int32_t llsr_mapping_close_loops(llsr_handle* h, const llsr_loop_config* loop_cfg, const llsr_pg_config* pg_cfg,
+                                 int32_t B, llsr_loop_report* loop_reps, llsr_pg_report* pg_reps, void* hip_stream);
+/* Graph b's poses (llsr_pg_poses of the slot's graph). */
+int32_t llsr_mapping_pose_graph_poses(llsr_handle* h, int32_t b, float* out6, int32_t cap);
 /* Host-only (no device): the pose glue llsr_mapping_batch applies per frame — OdometryToTransform
  * of FA's transformSum (tf2 round trip) into transform_sum, then transformAssociateToMap with the
  * given transformBefMapped / transformAftMapped into transform_tobe_mapped (and transform_incre,

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "llsr_handle.h"
+#include "llsr_pg.h"
 
 namespace llsr {
 // adjustOutlierCloud (FA:2600-2610): the IP outlier cloud of slot b (d.outl, [B][HW]) with
@@ -57,6 +58,7 @@ extern "C" int32_t llsr_mapping_reset(llsr_handle* h) {
   }
   mp.times.clear();
   mp.times_staged = false;
+  if (mp.pg) llsr_pg_reset(mp.pg, -1);
   const int B = (int)mp.slot.size();
   HIP_OK(h, hipMemset(mp.sm.d_deg, 0, sizeof(int) * B));      // isDegenerate = false (MO:285)
   HIP_OK(h, hipMemset(mp.sm.d_matP, 0, sizeof(float) * 36 * B));  // matP zeroed (MO:286)
@@ -73,6 +75,8 @@ void mapping_free(llsr_handle* h) {
   mp.vg = nullptr;
   if (mp.icp) llsr_icp_destroy(mp.icp);
   mp.icp = nullptr;
+  if (mp.pg) llsr_pg_destroy(mp.pg);
+  mp.pg = nullptr;
   mp.sm = llsr_handle::MapSmall{};
   mp.live = false;
 }
@@ -114,6 +118,51 @@ extern "C" int32_t llsr_mapping_init(llsr_handle* h, int32_t mo_mode, const llsr
   mp.sm = std::move(sm);
   mp.live = true;
   return llsr_mapping_reset(h);
+}
+
+// The slots' graphs start with room for 256 poses each and an envelope of four blocks per pose (two
+// for the odometry chain, two for loops); a full object is replaced by a larger one: twice the poses,
+// or twice the envelope up to what max_loops loops can need at most, (2 + max_loops) blocks per pose.
+static int32_t pg_regrow(llsr_handle* h, int32_t max_poses, int64_t max_blocks) {
+  auto& mp = h->mp;
+  int32_t k, l;
+  int64_t e;
+  llsr_pg_capacity(mp.pg, &k, &l, &e);
+  llsr_pg* g = llsr_pg_grown(mp.pg, std::max(k, max_poses), l, std::max(e, max_blocks));
+  if (!g) return fail(h, LLSR_ENOMEM, "pose graph: no memory to grow");
+  llsr_pg_destroy(mp.pg);
+  mp.pg = g;
+  return LLSR_OK;
+}
+
+// Keyframe `kp` of slot b into its graph (saveKeyFramesAndFactor's factors, MO:1641-1664)
+static int32_t pg_append_slot(llsr_handle* h, int b, const float* kp) {
+  auto& mp = h->mp;
+  int32_t rc = llsr_pg_append(mp.pg, b, kp, 1);
+  if (rc == LLSR_ERANGE) {  // poses or envelope: both double (a loop's span keeps its share)
+    int32_t k, l;
+    int64_t e;
+    llsr_pg_capacity(mp.pg, &k, &l, &e);
+    if ((rc = pg_regrow(h, 2 * k, 2 * e)) != LLSR_OK) return rc;
+    rc = llsr_pg_append(mp.pg, b, kp, 1);
+  }
+  return rc == LLSR_OK ? rc : fail(h, rc, std::string("pose graph: ") + llsr_pg_last_error(mp.pg));
+}
+
+// The loop factor of slot b's accepted report (MO:1086-1088)
+static int32_t pg_loop_slot(llsr_handle* h, int b, const llsr_loop_report& r) {
+  auto& mp = h->mp;
+  for (;;) {
+    const int32_t rc = llsr_pg_add_loop(mp.pg, b, r.latest_id, r.closest_id, r.pose_from, r.pose_to, r.variance);
+    if (rc == LLSR_OK) return rc;
+    int32_t k, l;
+    int64_t e;
+    llsr_pg_capacity(mp.pg, &k, &l, &e);
+    const int64_t most = (int64_t)(2 + l) * k;  // beyond this only the loop capacity can be what is full
+    if (rc != LLSR_ERANGE || e >= most) return fail(h, rc, std::string("pose graph: ") + llsr_pg_last_error(mp.pg));
+    const int32_t g = pg_regrow(h, k, std::min(2 * e, most));
+    if (g != LLSR_OK) return g;
+  }
 }
 
 // MapOptimization::run for the slots in `step` (their pose glue already applied by the caller);
@@ -290,6 +339,7 @@ static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::v
     if (times) llsr_map_set_keyframe_time(sl.map, kf, times[b]);  // thisPose6D.time (MO:1706)
     sl.keyposes.insert(sl.keyposes.end(), kp, kp + 6);
     sl.mo_frames += 1;
+    if (mp.pg && (rc = pg_append_slot(h, b, kp)) != LLSR_OK) return rc;
   }
 #ifdef LLSR_S2S_PROF
   {  // diagnostics build only: fail this call's MapOptimization part once, after its keyframes were
@@ -380,6 +430,7 @@ static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t*
       sl.mo_frames = sn.mo_frames; sl.lm_ran = sn.lm_ran; sl.n_cq = sn.n_cq; sl.n_sq = sn.n_sq;
       sl.cycle = sn.cycle; sl.lm = sn.lm; sl.mrep = sn.mrep; sl.now = sn.now;
       sl.keyposes.resize(snap[b].n_keyposes);
+      if (mp.pg) (void)llsr_pg_truncate(mp.pg, b, (int32_t)(snap[b].n_keyposes / 6));
       llsr_mapping::truncate_keyframes(sl.map, snap[b].n_keyframes);
       llsr_mapping::set_map_selection(sl.map, snap[b].sel);
     }
@@ -584,6 +635,76 @@ extern "C" int32_t llsr_mapping_set_key_poses(llsr_handle* h, int32_t b, const f
     for (int k = 0; k < 6; ++k)
       P.transformAftMapped[k] = P.transformLast[k] = P.transformTobeMapped[k] = latest_estimate6[k];
     for (int k = 0; k < 3; ++k) sl->robot[k] = P.transformAftMapped[3 + k];
+  }
+  return LLSR_OK;
+}
+
+// ---- the slots' pose graphs: the factor graph of MO:1086-1090 / 1612-1690 per slot ----
+extern "C" int32_t llsr_mapping_enable_pose_graph(llsr_handle* h, int32_t on, int32_t max_loops) {
+  if (!h) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (on && max_loops < 1) return fail(h, LLSR_EINVAL, "pose graph: max_loops must be >= 1");
+  HIP_OK(h, hipSetDevice(h->device));
+  if (mp.pg) llsr_pg_destroy(mp.pg);
+  mp.pg = nullptr;
+  if (!on) return LLSR_OK;
+  size_t most = 0;
+  for (const auto& sl : mp.slot) most = std::max(most, sl.keyposes.size() / 6);
+  int32_t max_poses = 256;
+  while ((size_t)max_poses < most) max_poses *= 2;
+  mp.pg = llsr_pg_create(h->device, (int32_t)mp.slot.size(), max_poses, max_loops, 4 * (int64_t)max_poses);
+  if (!mp.pg) return fail(h, LLSR_ENOMEM, "llsr_pg_create");
+  for (int b = 0; b < (int)mp.slot.size(); ++b) {  // the graphs start from the slots' key poses
+    const auto& kp = mp.slot[b].keyposes;
+    const int32_t rc = llsr_pg_append(mp.pg, b, kp.data(), (int32_t)(kp.size() / 6));
+    if (rc != LLSR_OK) {
+      const std::string msg = llsr_pg_last_error(mp.pg);
+      llsr_pg_destroy(mp.pg);
+      mp.pg = nullptr;
+      return fail(h, rc, "pose graph: " + msg);
+    }
+  }
+  return LLSR_OK;
+}
+
+extern "C" int32_t llsr_mapping_pose_graph_poses(llsr_handle* h, int32_t b, float* out6, int32_t cap) {
+  if (!h) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live || !mp.pg) return fail(h, LLSR_EINVAL, "llsr_mapping_enable_pose_graph not called");
+  if (b < 0 || b >= (int)mp.slot.size()) return fail(h, LLSR_ERANGE, "slot outside [0, max_batch)");
+  return llsr_pg_poses(mp.pg, b, out6, cap);
+}
+
+extern "C" int32_t llsr_mapping_close_loops(llsr_handle* h, const llsr_loop_config* loop_cfg,
+                                            const llsr_pg_config* pg_cfg, int32_t B, llsr_loop_report* loop_reps,
+                                            llsr_pg_report* pg_reps, void* hip_stream) {
+  if (!h || !loop_reps) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live || !mp.pg) return fail(h, LLSR_EINVAL, "llsr_mapping_enable_pose_graph not called");
+  int32_t rc = llsr_mapping_loop_closure(h, loop_cfg, B, loop_reps, hip_stream);
+  if (rc != LLSR_OK) return rc;
+  for (int b = 0; b < B; ++b) {
+    const llsr_loop_report& r = loop_reps[b];
+    if (!r.found || !r.accepted) continue;
+    if ((rc = pg_loop_slot(h, b, r)) != LLSR_OK) return rc;
+  }
+  hipStream_t s;
+  HIP_OK(h, enter(h, hip_stream, &s));
+  std::vector<llsr_pg_report> reps(mp.slot.size());
+  rc = llsr_pg_optimize(mp.pg, pg_cfg, reps.data(), s);  // every slot's graph in one set of launches
+  if (rc != LLSR_OK) return fail(h, rc, std::string("pose graph: ") + llsr_pg_last_error(mp.pg));
+  if (pg_reps) std::copy(reps.begin(), reps.begin() + B, pg_reps);
+  std::vector<float> poses;
+  for (int b = 0; b < (int)mp.slot.size(); ++b) {
+    if (!reps[b].moved) continue;
+    const int32_t K = llsr_pg_poses(mp.pg, b, nullptr, 0);
+    poses.resize(6 * (size_t)K);
+    llsr_pg_poses(mp.pg, b, poses.data(), K);
+    const float* kp = poses.data() + 6 * (size_t)(K - 1);
+    const float latest[6] = {kp[3], kp[4], kp[5], kp[0], kp[1], kp[2]};  // MO:1722-1733
+    rc = llsr_mapping_set_key_poses(h, b, poses.data(), K, latest);  // correctPoses (MO:1757-1785)
+    if (rc != LLSR_OK) return rc;
   }
   return LLSR_OK;
 }

@@ -174,6 +174,8 @@ struct LLSR_HIDDEN llsr_handle {
     bool times_staged = false;
     GrowBuf lsrc, ltgt;
     llsr_icp* icp = nullptr;
+    // the slots' pose graphs (llsr_mapping_enable_pose_graph): one object, graph b = slot b; NULL = off
+    llsr_pg* pg = nullptr;
   } mp;
   // IMU de-skew (llsr_stage_imu): device windows + per-slot carry and their pinned staging, allocated
   // on the first staging call; `armed` until a batch's feature stage consumes it

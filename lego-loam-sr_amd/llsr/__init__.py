@@ -54,6 +54,9 @@ EXPORTS = [
     "llsr_icp_last_times", "llsr_map_loop_submaps", "llsr_map_loop_closure",
     "llsr_icp_align_batch", "llsr_icp_last_passes", "llsr_mapping_stage_times", "llsr_mapping_keyframe_times",
     "llsr_mapping_loop_closure", "llsr_mapping_set_key_poses",
+    "llsr_pg_create", "llsr_pg_destroy", "llsr_pg_last_error", "llsr_pg_config_default", "llsr_pg_reset",
+    "llsr_pg_append", "llsr_pg_add_loop", "llsr_pg_optimize", "llsr_pg_poses",
+    "llsr_mapping_enable_pose_graph", "llsr_mapping_close_loops", "llsr_mapping_pose_graph_poses",
     "llsr_imu_init", "llsr_imu_callback", "llsr_imu_scan_window", "llsr_imu_deskew_host", "llsr_stage_imu",
     "llsr_fetch_imu_report", "llsr_set_imu_undistortion", "llsr_integrate_transformation_imu",
     "llsr_transform_to_end_imu", "llsr_first_scan_imu",
@@ -196,6 +199,19 @@ def lib():
         L.llsr_mapping_loop_closure.argtypes = [C.c_void_p, C.POINTER(_abi.LoopConfig), C.c_int32, C.c_void_p,
                                                 C.c_void_p]
         L.llsr_mapping_set_key_poses.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.llsr_pg_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
+        L.llsr_pg_destroy.argtypes = [C.c_void_p]
+        L.llsr_pg_last_error.argtypes = [C.c_void_p]
+        L.llsr_pg_config_default.argtypes = [C.POINTER(_abi.PgConfig)]
+        L.llsr_pg_reset.argtypes = [C.c_void_p, C.c_int32]
+        L.llsr_pg_append.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.llsr_pg_add_loop.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float]
+        L.llsr_pg_optimize.argtypes = [C.c_void_p, C.POINTER(_abi.PgConfig), C.c_void_p, C.c_void_p]
+        L.llsr_pg_poses.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.llsr_mapping_enable_pose_graph.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.llsr_mapping_close_loops.argtypes = [C.c_void_p, C.POINTER(_abi.LoopConfig), C.POINTER(_abi.PgConfig),
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llsr_mapping_pose_graph_poses.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         _loop = [C.POINTER(_abi.LoopConfig), C.c_void_p, C.c_double, C.POINTER(_abi.LoopReport)]
         L.llsr_map_loop_submaps.argtypes = [C.c_void_p] + _loop + [C.c_void_p, C.c_int64] * 4 + [C.c_void_p]
         L.llsr_map_loop_closure.argtypes = [C.c_void_p, C.c_void_p] + _loop + [C.c_void_p, C.c_int64] * 2 + [C.c_void_p]
@@ -215,7 +231,8 @@ def lib():
         for fn in EXPORTS:
             if fn not in ("llsr_last_error", "llsr_kernel_name", "llsr_destroy", "llsr_map_create",
                           "llsr_map_destroy", "llsr_map_last_error", "llsr_build_id", "llsr_icp_create",
-                          "llsr_icp_destroy", "llsr_icp_last_error"):
+                          "llsr_icp_destroy", "llsr_icp_last_error", "llsr_pg_create", "llsr_pg_destroy",
+                          "llsr_pg_last_error"):
                 getattr(L, fn).restype = C.c_int32
         L.llsr_destroy.restype = None
         L.llsr_map_create.restype = C.c_void_p
@@ -224,6 +241,9 @@ def lib():
         L.llsr_icp_create.restype = C.c_void_p
         L.llsr_icp_destroy.restype = None
         L.llsr_icp_last_error.restype = C.c_char_p
+        L.llsr_pg_create.restype = C.c_void_p
+        L.llsr_pg_destroy.restype = None
+        L.llsr_pg_last_error.restype = C.c_char_p
         _LIB = L
     return _LIB
 
@@ -603,6 +623,32 @@ class Pipeline:
         self._check(lib().llsr_mapping_set_key_poses(self._h, b, p.ctypes.data, len(p),
                                                      None if e is None else e.ctypes.data),
                     "llsr_mapping_set_key_poses")
+
+
+    def mapping_enable_pose_graph(self, on: bool = True, max_loops: int = 16):
+        """Keep a pose graph per slot (llsr_mapping_enable_pose_graph): every keyframe a slot saves from
+        now on is appended to it; mapping_close_loops optimises the graphs."""
+        self._check(lib().llsr_mapping_enable_pose_graph(self._h, int(bool(on)), max_loops),
+                    "llsr_mapping_enable_pose_graph")
+
+    def mapping_close_loops(self, B: int, cfg: _abi.LoopConfig | None = None, pg_cfg: _abi.PgConfig | None = None,
+                            stream: int = 0):
+        """The loop closure of slots 0 .. B - 1 through to the corrected key poses
+        (llsr_mapping_close_loops): the loop reports and the pose-graph reports, one dict per slot each."""
+        reps, pg = (_abi.LoopReport * B)(), (_abi.PgReport * B)()
+        self._check(lib().llsr_mapping_close_loops(self._h, C.byref(cfg) if cfg is not None else None,
+                                                   C.byref(pg_cfg) if pg_cfg is not None else None, B, reps, pg,
+                                                   C.c_void_p(stream)), "llsr_mapping_close_loops")
+        return [r.as_dict() for r in reps], [r.as_dict() for r in pg]
+
+    def mapping_pose_graph_poses(self, b: int) -> np.ndarray:
+        """Slot b's graph estimate, (K, 6) x, y, z, roll, pitch, yaw (llsr_mapping_pose_graph_poses)."""
+        n = lib().llsr_mapping_pose_graph_poses(self._h, b, None, 0)
+        if n < 0:
+            self._check(n, "llsr_mapping_pose_graph_poses")
+        out = np.zeros((max(n, 1), 6), np.float32)
+        lib().llsr_mapping_pose_graph_poses(self._h, b, out.ctypes.data, n)
+        return out[:n].copy()
 
 
 def mapping_associate(transform_sum_fa, bef, aft):
@@ -1010,6 +1056,72 @@ def icp_align_host(src, tgt, cfg: _abi.LoopConfig | None = None) -> dict:
     r = res.as_dict()
     r["aligned"] = out[:len(a)]
     return r
+
+
+def pg_config(**kw) -> _abi.PgConfig:
+    """llsr_pg_config_default (GTSAM's NonlinearOptimizerParams defaults), fields overridden by keyword."""
+    c = _abi.PgConfig()
+    lib().llsr_pg_config_default(C.byref(c))
+    for k, v in kw.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        setattr(c, k, v)
+    return c
+
+
+class PoseGraph:
+    """P pose graphs optimised together (llsr_pg, include/llsr.h). device None runs the
+    same loop bodies on the host (LLSR_PG_HOST). Poses are (x, y, z, roll, pitch, yaw) float32 rows."""
+
+    def __init__(self, P: int, max_poses: int, max_loops: int, max_envelope_blocks: int | None = None,
+                 device: int | None = 0):
+        if max_envelope_blocks is None:
+            max_envelope_blocks = (2 + max_loops) * max_poses
+        self.P = P
+        self._w = lib().llsr_pg_create(_abi.LLSR_PG_HOST if device is None else device, P, max_poses, max_loops,
+                                       max_envelope_blocks)
+        if not self._w:
+            raise LlsrError("llsr_pg_create failed: bad capacities, no HIP device or no memory")
+
+    def close(self):
+        if getattr(self, "_w", None):
+            lib().llsr_pg_destroy(self._w)
+            self._w = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc: int, what: str):
+        if rc < 0:
+            e = LlsrError(f"{what} failed ({rc}): {lib().llsr_pg_last_error(self._w).decode()}")
+            e.code = rc
+            raise e
+
+    def reset(self, p: int = -1):
+        self._check(lib().llsr_pg_reset(self._w, p), "llsr_pg_reset")
+
+    def append(self, p: int, poses6):
+        a = np.ascontiguousarray(poses6, np.float32).reshape(-1, 6)
+        self._check(lib().llsr_pg_append(self._w, p, a.ctypes.data, len(a)), "llsr_pg_append")
+
+    def add_loop(self, p: int, from_id: int, to_id: int, pose_from6, pose_to6, variance: float):
+        """pose_from6 / pose_to6 / variance as llsr_loop_constraint gives them (GTSAM's axis order)."""
+        a, b = (np.ascontiguousarray(x, np.float32).reshape(6) for x in (pose_from6, pose_to6))
+        self._check(lib().llsr_pg_add_loop(self._w, p, from_id, to_id, a.ctypes.data, b.ctypes.data,
+                                           C.c_float(variance)), "llsr_pg_add_loop")
+
+    def optimize(self, cfg: _abi.PgConfig | None = None, stream: int = 0) -> list:
+        reps = (_abi.PgReport * self.P)()
+        self._check(lib().llsr_pg_optimize(self._w, C.byref(cfg) if cfg is not None else None, reps,
+                                           C.c_void_p(stream)), "llsr_pg_optimize")
+        return [r.as_dict() for r in reps]
+
+    def poses(self, p: int) -> np.ndarray:
+        n = lib().llsr_pg_poses(self._w, p, None, 0)
+        self._check(n, "llsr_pg_poses")
+        out = np.zeros((max(n, 1), 6), np.float32)
+        lib().llsr_pg_poses(self._w, p, out.ctypes.data, n)
+        return out[:n].copy()
 
 
 class Icp:

@@ -370,6 +370,28 @@ class LoopReport(C.Structure):
         return d
 
 
+LLSR_PG_HOST = -1
+PG_STATES = ("clean", "absolute_tol", "relative_tol", "iterations", "error_rose", "failed")
+
+
+class PgConfig(C.Structure):
+    """llsr_pg_config (include/llsr.h): the Gauss-Newton stop rule."""
+    _fields_ = [("max_iterations", C.c_int32), ("pad", C.c_int32), ("relative_error_tol", C.c_double),
+                ("absolute_error_tol", C.c_double)]
+
+
+class PgReport(C.Structure):
+    """llsr_pg_report (include/llsr.h): one graph after llsr_pg_optimize."""
+    _fields_ = [("state", C.c_int32), ("iterations", C.c_int32), ("error_before", C.c_double),
+                ("error_after", C.c_double), ("poses", C.c_int32), ("loops", C.c_int32), ("ms", C.c_float),
+                ("moved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"state": int(self.state), "iterations": int(self.iterations), "error_before": float(self.error_before),
+                "error_after": float(self.error_after), "poses": int(self.poses), "loops": int(self.loops),
+                "ms": float(self.ms), "moved": bool(self.moved)}
+
+
 class MappingSlot(C.Structure):
     """llsr_mapping_slot (include/llsr.h): one sequence's MapOptimization state after the last call."""
     _fields_ = [("frames", C.c_int32), ("mo_frames", C.c_int32), ("keyframes", C.c_int32), ("lm_ran", C.c_int32),
