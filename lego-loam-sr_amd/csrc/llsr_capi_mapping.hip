@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "llsr_handle.h"
+#include "llsr_icp.h"
 #include "llsr_pg.h"
 
 namespace llsr {
@@ -609,10 +610,7 @@ extern "C" int32_t llsr_mapping_loop_closure(llsr_handle* h, const llsr_loop_con
       llsr_loop_report& rep = reps[found[i]];
       const auto& kp = mp.slot[found[i]].keyposes;
       rep.icp = res[i];
-      rep.accepted = rep.icp.converged && !(rep.icp.fitness > (double)cfg->fitness_score);  // MO:1038-1040
-      if (rep.accepted)
-        llsr_loop_constraint(rep.icp.T, kp.data() + 6 * (size_t)rep.latest_id, kp.data() + 6 * (size_t)rep.closest_id,
-                             rep.icp.fitness, rep.pose_from, rep.pose_to, &rep.variance);
+      llsr_loop::loop_accept(cfg, kp.data() + 6 * (size_t)rep.latest_id, kp.data() + 6 * (size_t)rep.closest_id, &rep);
     }
   }
   const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -12,6 +12,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/llsr.h"
 #include "llsr_cell.h"
 #include "llsr_eigen.h"
 #include "llsr_libm.h"
@@ -576,7 +577,7 @@ LLSR_HD void fitsum_body(const IcpArgs& a) {
   a.st->n_fit = n;
 }
 
-// ---- the serial host driver ------------------------------------------------------------------------
+// ---- the serial host side ---------------------------------------------------------------------------
 // The target's grid in the layout of llsr_grid.h, built serially: cells claim table slots in point
 // order, ranges are laid out in slot order, points are placed in point order (the order inside a
 // cell never changes a result: ties go by the original index).
@@ -610,40 +611,6 @@ inline void grid_build_host(const float* tgt4, int n, int log2T, llsr::CellSlot*
   delete[] slot;
   box[0] = box[1] = box[2] = kBoxEmptyLo;
   box[3] = box[4] = box[5] = kBoxEmptyHi;
-}
-
-// The loop over heap buffers laid out as the device's (a.* sized by the comments of IcpArgs): every
-// launch of llsr_icp_align becomes a loop over its (block, thread) range calling the same body.
-inline void icp_run_host(const IcpArgs& a) {
-  state_init(a.st);
-  for (int blk = 0; blk < blocks_for(a.n_tgt, kCorrBlock); ++blk)
-    for (int t = 0; t < kCorrBlock; ++t) {
-      int c[3];
-      if (!box_cell(a, point_of(blk, t, kCorrBlock), c)) continue;
-      for (int k = 0; k < 3; ++k) {
-        if (c[k] < a.box[k]) a.box[k] = c[k];
-        if (c[k] > a.box[3 + k]) a.box[3 + k] = c[k];
-      }
-    }
-  for (size_t k = 0; k < 4 * (size_t)a.n_src; ++k) a.work4[k] = a.src4[k];
-  while (a.st->state == kStateNone) {
-    for (int blk = 0; blk < blocks_for(a.n_src, kCorrBlock); ++blk)
-      for (int t = 0; t < kCorrBlock; ++t) corr_body(a, point_of(blk, t, kCorrBlock));
-    int pos = 0;  // the scan of k_icp_pack, serially
-    for (int tile = 0; tile < blocks_for(a.n_src, kPackBlock); ++tile)
-      for (int t = 0; t < kPackBlock; ++t) {
-        const int i = point_of(tile, t, kPackBlock);
-        if (pack_keep(a, i)) pack_write(a, i, pos++);
-      }
-    a.st->n_pairs = pos;
-    for (int lane = 0; lane < kLaneBlock; ++lane) means_body(a, lane);
-    for (int blk = 0; blk < blocks_for(9 * sigma_blocks_max(a.n_src), kCorrBlock); ++blk)
-      for (int t = 0; t < kCorrBlock; ++t) sigma_body(a, point_of(blk, t, kCorrBlock));
-    finish_body(a);
-  }
-  for (int blk = 0; blk < blocks_for(a.n_src, kCorrBlock); ++blk)
-    for (int t = 0; t < kCorrBlock; ++t) fit_body(a, point_of(blk, t, kCorrBlock));
-  fitsum_body(a);
 }
 
 // ---- the batch form (DESIGN.md §16 "Batch form"): P alignments in one set of launches --------------
@@ -748,11 +715,13 @@ inline void icp_batch_entry(const IcpBatchLayout& L, const IcpBatchBuffers& b, c
   a->aligned4 = b.aligned4 + 4 * so;
 }
 
-// The batch launches of llsr_icp_align_batch as loops over their (block.x, block.y, thread) ranges,
-// over a table whose grids were built with grid_build_host at the batch's log2T. Returns the number
-// of passes of the loop, or -1 when a problem is still unfinished after max_passes (which the stop
-// rule excludes).
-inline int icp_run_batch_host(const IcpArgs* tab, int P) {
+// The one serial driver: the batch launches of llsr_icp_align_batch as loops over their (block.x,
+// block.y, thread) ranges calling the same bodies, over a table whose grids were built with
+// grid_build_host at each entry's log2T. A single alignment is a table of one (llsr_icp_align_host),
+// and that is also the serial statement of llsr_icp_align's launches: at P = 1 every extent is the
+// problem's own and the problem is live until the loop ends. Returns the number of passes of the loop,
+// or -1 when a problem is still unfinished after max_passes (which the stop rule excludes).
+inline int icp_run_host(const IcpArgs* tab, int P) {
   const IcpBatchDims dims = icp_batch_dims(tab, P);
   int live = P;
   for (int p = 0; p < P; ++p) init_body(tab[p]);
@@ -849,5 +818,13 @@ inline void loop_constraint(const float* T16, const float* latest, const float* 
   pose_to[0] = closest[2]; pose_to[1] = closest[0]; pose_to[2] = closest[1];
   pose_to[3] = closest[5]; pose_to[4] = closest[3]; pose_to[5] = closest[4];
   *variance = (float)fitness;
+}
+// MO:1038-1040 on rep->icp, and the constraint of an accepted alignment between the latest and the
+// closest key pose (x, y, z, roll, pitch, yaw each)
+inline void loop_accept(const llsr_loop_config* cfg, const float* latest6, const float* closest6,
+                        llsr_loop_report* rep) {
+  rep->accepted = rep->icp.converged && !(rep->icp.fitness > (double)cfg->fitness_score);
+  if (rep->accepted)
+    loop_constraint(rep->icp.T, latest6, closest6, rep->icp.fitness, rep->pose_from, rep->pose_to, &rep->variance);
 }
 }  // namespace llsr_loop

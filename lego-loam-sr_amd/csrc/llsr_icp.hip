@@ -81,8 +81,8 @@ bool icp_bad_args(const float* src4, int32_t n_src, const float* tgt4, int32_t n
 
 }  // namespace
 
-// The serial statement of the alignment: heap buffers of the device layout's sizes, the loop of
-// llsr_icp.h over them.
+// The serial statement of the alignment: heap buffers of exactly icp_sizes, the problem's own table
+// size, the one serial driver of llsr_icp.h on a table of that one entry.
 extern "C" int32_t llsr_icp_align_host(const float* src4, int32_t n_src, const float* tgt4, int32_t n_tgt,
                                        const llsr_loop_config* cfg, llsr_icp_result* res, float* aligned4) {
   if (icp_bad_args(src4, n_src, tgt4, n_tgt, cfg, res)) return LLSR_EINVAL;
@@ -101,7 +101,7 @@ extern "C" int32_t llsr_icp_align_host(const float* src4, int32_t n_src, const f
   a.part = part.data(); a.st = &st; a.aligned4 = aligned4 ? aligned4 : al.data();
   a.n_src = n_src; a.n_tgt = n_tgt; a.log2T = log2T;
   icp_params(cfg, &a);
-  icp_run_host(a);
+  if (icp_run_host(&a, 1) < 1) return LLSR_EIO;
   icp_result(st, res);
   return LLSR_OK;
 }

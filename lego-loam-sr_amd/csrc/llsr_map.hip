@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/llsr.h"
+#include "llsr_icp.h"
 #include "llsr_isort.h"
 #include "llsr_libm.h"
 #include "llsr_mapping.h"
@@ -1452,11 +1453,7 @@ extern "C" int32_t llsr_map_loop_closure(llsr_map* m, llsr_icp* w, const llsr_lo
                       reinterpret_cast<const float*>(lc.target), (int32_t)rep->n_target, cfg, &rep->icp, d_aligned, s);
   if (rc != LLSR_OK) return mfail(m, rc, std::string("loop closure: ") + llsr_icp_last_error(w));
   if ((rc = loop_copy_out(m, lc.target_ds, rep->n_target_ds, d_target_ds, s)) != LLSR_OK) return rc;
-  // MO:1038-1040
-  rep->accepted = rep->icp.converged && !(rep->icp.fitness > (double)cfg->fitness_score);
-  if (rep->accepted)
-    llsr_loop_constraint(rep->icp.T, m->kf[rep->latest_id].pose, m->kf[rep->closest_id].pose, rep->icp.fitness,
-                         rep->pose_from, rep->pose_to, &rep->variance);
+  llsr_loop::loop_accept(cfg, m->kf[rep->latest_id].pose, m->kf[rep->closest_id].pose, rep);
   MAP_OK(m, hipStreamSynchronize(s));
   rep->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return LLSR_OK;

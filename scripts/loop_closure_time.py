@@ -88,10 +88,12 @@ def main():
         "n_target_ds": int(r["n_target_ds"]), "iterations": int(r["iterations"]),
         "state": llsr._abi.ICP_STATES[int(r["state"])], "converged": bool(r["converged"]), "fitness": float(r["fitness"]),
         "accepted": bool(r["accepted"]), "n_pairs_last": int(r["n_pairs_last"]),
-        "loop_closure_call_ms": statistics.median(call_ms), "icp_align_device_ms": statistics.median(align_ms),
+        "loop_closure_call_ms": statistics.median(call_ms), "loop_closure_call_ms_min": min(call_ms),
+        "loop_closure_call_ms_max": max(call_ms), "icp_align_device_ms": statistics.median(align_ms),
         "corr_ms_per_iteration": corr / it, "solve_ms_per_iteration": solve / it,
         "iteration_bound_by": "correspondence search" if corr > solve else "solve (pack, chains, estimate)",
-        "icp_align_host_ms": statistics.median(host_ms), "host_equals_device_bits": same,
+        "icp_align_host_ms": statistics.median(host_ms), "icp_align_host_ms_min": min(host_ms),
+        "icp_align_host_ms_max": max(host_ms), "host_equals_device_bits": same,
         "device_over_host": statistics.median(align_ms) / statistics.median(host_ms),
     }
     print(json.dumps(out, indent=1))

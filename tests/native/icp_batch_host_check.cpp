@@ -1,11 +1,12 @@
-// icp_batch_host_check.cpp — CPU check of the batch form of the loop-closure ICP (csrc/llsr_icp.h,
-// DESIGN.md §16 "Batch form"), run by tests/test_icp_batch_native.py under AddressSanitizer / UBSan.
-// icp_run_batch_host — the launches of llsr_icp_align_batch as loops over their (block.x, block.y,
-// thread) ranges — runs over one table built by icp_batch_layout / icp_batch_entry, the functions the
-// device call builds its table with, over heap buffers of exactly the sizes the layout gives. The
-// batch mixes an empty source, an empty target, 2, 3 and 681 kept pairs, and a 7-point target next to
-// 3000-point ones, in both orders; every problem's state, final, fitness and aligned cloud must equal
-// icp_run_host on that problem alone (its own table size), bit for bit.
+// icp_batch_host_check.cpp — CPU check of the loop-closure ICP's host driver on a table of many
+// problems (csrc/llsr_icp.h, DESIGN.md §16 "Batch form"), run by tests/test_icp_batch_native.py under
+// AddressSanitizer / UBSan. icp_run_host — the batch launches of llsr_icp.hip as loops over their
+// (block.x, block.y, thread) ranges — runs over one table built by icp_batch_layout / icp_batch_entry, the
+// functions the device call builds its table with, over heap buffers of exactly the sizes the layout
+// gives. The batch mixes an empty source, an empty target, 2, 3 and 681 kept pairs, and a 7-point
+// target next to 3000-point ones, in both orders; every problem's state, final, fitness and aligned
+// cloud must equal the same driver on that problem as a hand-filled table of one (exact icp_sizes
+// buffers, its own table size), bit for bit: no result depends on log2T, the slices or the order.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -70,7 +71,7 @@ static Problem make(int n_tgt, int kept, int n_far) {
   return pr;
 }
 
-struct Alone {  // one problem through icp_run_host, buffers at icp_sizes
+struct Alone {  // one problem as a table of one through icp_run_host, buffers at icp_sizes
   IcpSizes z;
   Heap<llsr::CellSlot> tab;
   Heap<float> cells, work, d2, ps, pd, part, al;
@@ -86,7 +87,7 @@ struct Alone {  // one problem through icp_run_host, buffers at icp_sizes
     a.n_src = (int)pr.src.size() / 4; a.n_tgt = (int)pr.tgt.size() / 4; a.log2T = z.log2T;
     a.max_iterations = pr.max_iterations; a.eps_t = 1e-6; a.eps_f = 1e-6; a.mcd2 = 100.0 * 100.0;
     grid_build_host(a.tgt4, a.n_tgt, a.log2T, tab.p, cells.p, box.p);
-    icp_run_host(a);
+    REQUIRE(icp_run_host(&a, 1) >= 1);
   }
 };
 
@@ -124,7 +125,7 @@ static int run_batch(const std::vector<Problem>& all, const std::vector<Alone*>&
                     a->box);
   }
   REQUIRE(part_at == L.part);
-  const int passes = icp_run_batch_host(args.p, P);
+  const int passes = icp_run_host(args.p, P);
   REQUIRE(passes >= 1);
   for (int p = 0; p < P; ++p) {
     const IcpState& g = st.p[p];

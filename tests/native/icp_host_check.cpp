@@ -7,8 +7,8 @@
 //   2. the chains: means_body / sigma_body / finish_body over their launch shapes against
 //      umeyama3_host on the same pairs, at the depth-block edges of sigma;
 //   3. the index mappings: sigma_blocks_max bounds the block count for every n, sigma_lane's ranges
-//      tile [0, n) once per entry, and the whole driver (every launch's (block, thread) loop) runs
-//      over exact-size buffers for the launch shapes the tests use.
+//      tile [0, n) once per entry, and the whole driver (every launch's (block, thread) loop, on a
+//      table of one entry) runs over exact-size buffers for the launch shapes the tests use.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -239,7 +239,7 @@ static void mapping_cases() {
       }
     }
     Run r(src, tgt);
-    icp_run_host(r.a);
+    REQUIRE(icp_run_host(&r.a, 1) >= 1);
     REQUIRE(r.a.st->state != kStateNone);
     REQUIRE(r.a.st->n_pairs <= sh[0]);
     if (sh[0] >= 3 && sh[1] >= 3) REQUIRE(r.a.st->iterations >= 1);

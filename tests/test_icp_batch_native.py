@@ -1,7 +1,8 @@
-"""CPU: the batch form of the loop-closure ICP (csrc/llsr_icp.h, DESIGN.md §16 "Batch form") in a
-stand-alone program under AddressSanitizer / UBSan — tests/native/icp_batch_host_check.cpp:
-icp_run_batch_host over a table built by the device call's own layout functions, on heap buffers of
-exactly the layout's sizes, against icp_run_host on every problem alone, bit for bit."""
+"""CPU: the loop-closure ICP's host driver on a table of many problems (csrc/llsr_icp.h, DESIGN.md §16
+"Batch form") in a stand-alone program under AddressSanitizer / UBSan —
+tests/native/icp_batch_host_check.cpp: icp_run_host over a table built by the device call's own layout
+functions, on heap buffers of exactly the layout's sizes, against the same driver on every problem as a
+table of one at its own table size, bit for bit."""
 import os
 import subprocess
 

@@ -1,7 +1,7 @@
 """CPU: the loop-closure ICP's shared host / device bodies (csrc/llsr_icp.h) in a stand-alone program
 under AddressSanitizer / UBSan — tests/native/icp_host_check.cpp: the shell search against a
-brute-force loop, the chains against umeyama3_host, and every launch's (block, thread) mapping over
-heap buffers of exactly the device workspace's sizes."""
+brute-force loop, the chains against umeyama3_host, and every launch's (block, thread) mapping (the
+one driver, icp_run_host, on a table of one) over heap buffers of exactly icp_sizes."""
 import os
 import subprocess
 
