@@ -30,6 +30,7 @@
 #include "llsr_grid.h"
 #include "llsr_isort.h"
 #include "llsr_s2s.h"
+#include "llsr_search.h"  // l2, kMaxShell, kMulti, nn1_shells, nn1_scan, nn1_block_multi
 
 namespace llsr {
 
@@ -41,7 +42,6 @@ using llsr_libm::sqrt_;
 
 namespace {
 
-constexpr int kMaxShell = 2;  // grid shells searched before the exact block-wide scan (queries in sparse regions)
 constexpr int kFbMax = 256;       // queries per kNN iteration whose shells did not settle (block scan)
 constexpr int kIx = 5;            // ints per query in S2SArgs::idx
 constexpr int kWalkBudget = 200;  // per-lane surf walk steps before the whole-wave walk takes over
@@ -66,119 +66,6 @@ __device__ __forceinline__ float4 to_start(const float* t, float4 pi) {
 // (last - sel)^2 as written at FA:1609-1614
 __device__ __forceinline__ float sqdis(float4 a, float4 b) {
   return (a.x - b.x) * (a.x - b.x) + (a.y - b.y) * (a.y - b.y) + (a.z - b.z) * (a.z - b.z);
-}
-
-// nanoflann L2_Simple (query - point), accumulated from 0
-__device__ __forceinline__ float l2(float4 q, float4 p) {
-  float d = 0.0f, t;
-  t = q.x - p.x; d += t * t;
-  t = q.y - p.y; d += t * t;
-  t = q.z - p.z; d += t * t;
-  return d;
-}
-
-// Nearest neighbour of q in grid g of problem p (KdTreeFLANN::nearestKSearch, k = 1; ties ->
-// lower index) over growing shells of 1 m cells. Returns true once the searched shells provably
-// contain the nearest point or nothing nearer than dist_sqr can remain outside them; false when
-// kMaxShell shells do not settle it (the caller then scans the whole cloud, nn1_block).
-// (bi, bd) may start from a known point of the cloud (the previous kNN pass's answer: a real
-// candidate, so the lexicographic minimum is unchanged) — cells farther than it are not probed.
-__device__ bool nn1_shells(const CellGrid& g, int p, float4 q, float dist_sqr, int& bi, float& bd) {
-  const CellSlot* tab = g.table(p);
-  const float4* pts = g.cells(p);
-  const int cx = cell_coord(q.x), cy = cell_coord(q.y), cz = cell_coord(q.z);
-  // squared gap of q to the cell slab at offset dd along one axis, rounded as l2 rounds: a point
-  // of that slab has |fl(q - p)| >= this gap (rounding is monotone and symmetric)
-  auto gap2 = [](float v, int c, int dd) {
-    const float g = dd < 0 ? v - (float)(c + dd + 1) : dd > 0 ? (float)(c + dd) - v : 0.0f;
-    return g * g;
-  };
-  for (int h = 0; h <= kMaxShell; ++h) {
-    for (int dx = -h; dx <= h; ++dx)
-      for (int dy = -h; dy <= h; ++dy) {
-        const int step = (h == 0 || dx == -h || dx == h || dy == -h || dy == h) ? 1 : 2 * h;
-        const float lxy = gap2(q.x, cx, dx) + gap2(q.y, cy, dy);
-        for (int dz = -h; dz <= h; dz += step) {
-          // a cell whose every point is farther than bd cannot change the (d, index) minimum, and
-          // one with none nearer than dist_sqr cannot give a correspondence (finish rejects nd >= it)
-          const float lb = lxy + gap2(q.z, cz, dz);
-          if (lb > bd || lb >= dist_sqr) continue;
-          const int s = grid_find(tab, g.log2T, cell_key(cx + dx, cy + dy, cz + dz));
-          if (s < 0) continue;
-          const int st = tab[s].start, n = tab[s].count;
-          for (int j = st; j < st + n; ++j) {
-            const float4 c = pts[j];
-            const float d = l2(q, c);
-            const int id = (int)fbits(c.w);
-            if (nn_before(d, id, bd, bi)) { bd = d; bi = id; }
-          }
-        }
-      }
-    // every point outside the searched block is at least r away (float slack 1e-5)
-    float r = q.x - (float)(cx - h);
-    r = fminf(r, (float)(cx + h + 1) - q.x);
-    r = fminf(r, q.y - (float)(cy - h));
-    r = fminf(r, (float)(cy + h + 1) - q.y);
-    r = fminf(r, q.z - (float)(cz - h));
-    r = fminf(r, (float)(cz + h + 1) - q.z);
-    const float r2 = r * r * (1.0f - 1e-5f);
-    if (bd < r2 || r2 >= dist_sqr) return true;
-  }
-  return false;
-}
-
-// Exact nearest neighbour by a scan in index order with strict '<' (ties -> lower index, as the
-// shells).
-__device__ __forceinline__ void nn1_scan(const float4* pts, int n, float4 q, int& bi, float& bd) {
-  bd = INFINITY;
-  bi = INT_MAX;
-  for (int k = 0; k < n; ++k) {
-    const float d = l2(q, pts[k]);
-    if (d < bd) { bd = d; bi = k; }
-  }
-}
-
-// nn1_scan for up to kMulti queries at once by the whole block: each thread scans an interleaved
-// slice of the cloud in index order against every query, then each query's (d, index) minima are
-// reduced with the index tie-break — equal to nn1_scan per query, with one pass over the cloud
-// for kMulti queries. Contains barriers: every thread of the block must call it.
-constexpr int kMulti = 2;  // 2 (from 4): 113 instead of 166 spilled VGPRs at the 4-waves bound
-template <int kNT>
-__device__ void nn1_block_multi(const float4* pts, int n, const float4* qs, int nq, int* bi, float* bd,
-                                float (*red_d)[kNT / 64], int (*red_i)[kNT / 64]) {
-  float d[kMulti];
-  int id[kMulti];
-#pragma unroll
-  for (int j = 0; j < kMulti; ++j) { d[j] = INFINITY; id[j] = INT_MAX; }
-  for (int k = threadIdx.x; k < n; k += blockDim.x) {
-    const float4 p = pts[k];
-#pragma unroll
-    for (int j = 0; j < kMulti; ++j)
-      if (j < nq) {
-        const float dd = l2(qs[j], p);
-        if (dd < d[j]) { d[j] = dd; id[j] = k; }
-      }
-  }
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-  for (int j = 0; j < kMulti; ++j) {
-    for (int off = 32; off; off >>= 1) {
-      const float od = __shfl_xor(d[j], off, 64);
-      const int oi = __shfl_xor(id[j], off, 64);
-      if (nn_before(od, oi, d[j], id[j])) { d[j] = od; id[j] = oi; }
-    }
-    if (lane_id() == 0) { red_d[j][w] = d[j]; red_i[j][w] = id[j]; }
-  }
-  __syncthreads();
-  for (int j = 0; j < nq; ++j) {
-    float bdj = red_d[j][0];
-    int bij = red_i[j][0];
-    for (int k = 1; k < nw; ++k)
-      if (nn_before(red_d[j][k], red_i[j][k], bdj, bij)) { bdj = red_d[j][k]; bij = red_i[j][k]; }
-    bd[j] = bdj;
-    bi[j] = bij;
-  }
-  __syncthreads();
 }
 
 // findCorrespondingCornerFeatures search (FA:1587-1648) around the nearest neighbour nn (squared

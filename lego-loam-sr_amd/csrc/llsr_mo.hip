@@ -34,6 +34,7 @@
 #include "llsr_grid.h"
 #include "llsr_lm.h"
 #include "llsr_mo.h"
+#include "llsr_search.h"  // Best5, knn5
 
 // LLSR_S2M_DBG stage stops of k_s2m_solve exist only in the diagnostic build (make prof)
 #ifdef LLSR_S2S_PROF
@@ -52,75 +53,6 @@ using llsr_libm::sinf_;
 using llsr_libm::sqrt_;
 
 namespace {
-
-struct Best5 {
-  float d[5];
-  int i[5];
-};
-
-// The 27 neighbour cells in the order kNN-5 visits them: the query's own cell, the 6 face
-// neighbours, the 12 edge and the 8 corner neighbours (packed as (dx+1) | (dy+1) << 2 | (dz+1) << 4),
-// so the 5th-best distance tightens early and prunes the farther cells.
-__constant__ unsigned char kCellOrder[27] = {
-    21,                                          // (0, 0, 0)
-    20, 22, 17, 25, 5, 37,                       // faces
-    16, 18, 24, 26, 4, 6, 36, 38, 1, 9, 33, 41,  // edges
-    0, 2, 8, 10, 32, 34, 40, 42};                // corners
-
-// kNN-5 with d^2 < 1.0 around q in one map; returns true when five were found.
-// The result is the five smallest (d^2, index) pairs of the cells' points with d^2 < 1.0, in any
-// visiting order. A cell is skipped when no point in it can enter that set: its box lies at squared
-// distance LB from q, every point's float d^2 (three rounded differences, squares and sums) is at
-// least LB (1 - 5 eps) minus the rounding of the box gaps (< 1e-7 absolute), so a cell with
-// LB > lim (1 + 1e-5) + 4e-6 holds only points with d^2 > lim, where lim = 1.0, or the current 5th
-// distance once five are held (a tie at lim would need d^2 == lim). Exact, therefore, and typically
-// 7 of the 27 cells are probed (the center, the faces and a few edges; tests/test_gpu_mo.py).
-__device__ bool knn5(const CellSlot* __restrict__ tab, int log2T, const float4* __restrict__ pts,
-                     float qx, float qy, float qz, Best5& b) {
-#pragma unroll
-  for (int k = 0; k < 5; ++k) { b.d[k] = INFINITY; b.i[k] = INT_MAX; }
-  const int cx = cell_coord(qx), cy = cell_coord(qy), cz = cell_coord(qz);
-  // distances from q to its cell's lower / upper faces per axis (cell_coord's sentinel cell for
-  // NaN / huge coordinates: gaps become NaN / huge, no cell is skipped wrongly since LB > lim fails
-  // for NaN and a huge q finds nothing anyway)
-  const float lx = qx - floorf(qx), ly = qy - floorf(qy), lz = qz - floorf(qz);
-  const float ux = 1.0f - lx, uy = 1.0f - ly, uz = 1.0f - lz;
-  // cells visited one at a time (not unrolled): keeps the kernel's VGPRs low, which beat issuing
-  // all probes up front on MI355X (latency-bound gathers, 8 waves per SIMD)
-#pragma unroll 1
-  for (int c = 0; c < 27; ++c) {
-    const int o = kCellOrder[c];
-    const int ox = (o & 3) - 1, oy = ((o >> 2) & 3) - 1, oz = (o >> 4) - 1;
-    const float gx = ox < 0 ? lx : (ox > 0 ? ux : 0.0f);
-    const float gy = oy < 0 ? ly : (oy > 0 ? uy : 0.0f);
-    const float gz = oz < 0 ? lz : (oz > 0 ? uz : 0.0f);
-    const float lb = gx * gx + gy * gy + gz * gz;
-    const float lim = b.d[4] < 1.0f ? b.d[4] : 1.0f;
-    if (lb > lim * 1.00001f + 4e-6f) continue;
-    const int s = grid_find(tab, log2T, cell_key(cx + ox, cy + oy, cz + oz));
-    if (s < 0) continue;
-    const int st = tab[s].start, n = tab[s].count;
-    float4 pn = n > 0 ? pts[st] : make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int j = st; j < st + n; ++j) {
-      const float4 p = pn;  // the next point's load is in flight while this one is tested
-      if (j + 1 < st + n) pn = pts[j + 1];
-      float d = 0.0f;
-      float t = qx - p.x; d += t * t;  // nanoflann L2 accumulation order
-      t = qy - p.y; d += t * t;
-      t = qz - p.z; d += t * t;
-      const int id = (int)fbits(p.w);
-      if (!(d < 1.0f) || !nn_before(d, id, b.d[4], b.i[4])) continue;
-      b.d[4] = d; b.i[4] = id;
-#pragma unroll
-      for (int k = 4; k > 0; --k)
-        if (nn_before(b.d[k], b.i[k], b.d[k - 1], b.i[k - 1])) {
-          const float td = b.d[k]; b.d[k] = b.d[k - 1]; b.d[k - 1] = td;
-          const int ti = b.i[k]; b.i[k] = b.i[k - 1]; b.i[k - 1] = ti;
-        }
-    }
-  }
-  return b.d[4] < 1.0f;
-}
 
 // pointAssociateToMap (MO:606-620) with the cached sin/cos of transformTobeMapped.
 struct Assoc {
