@@ -552,18 +552,35 @@ __device__ __forceinline__ uint32_t st_push(uint32_t F, bool one, bool cand) {
   return lo | hi;
 }
 
-__device__ __forceinline__ bool add_test(const float4* __restrict__ full, int cell, int nb) {
-  const float4 p = full[cell], q = full[nb];
-  const float r = sqrt_(p.x * p.x + p.y * p.y + p.z * p.z);
+// add_test's two halves: the norm of the cell's point is shared by the forward (j - 2) and the
+// backward (j + 2) test of a cell
+struct AddPt { float x, y, z; };  // a cell's point without its intensity (12 of the 16 bytes)
+__device__ __forceinline__ AddPt add_load(const float4* __restrict__ full, int cell) {
+  const float* f = reinterpret_cast<const float*>(full + cell);
+  return AddPt{f[0], f[1], f[2]};
+}
+__device__ __forceinline__ float add_norm(const AddPt& p) { return sqrt_(p.x * p.x + p.y * p.y + p.z * p.z); }
+__device__ __forceinline__ bool add_test(const AddPt& p, float r, const AddPt& q) {
   const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
   const float dr = sqrt_(dx * dx + dy * dy + dz * dz);
   return (double)dr <= 0.061 * (double)r && (double)dz <= 0.1;
 }
 
-// 8 waves per SIMD (45 VGPRs, no spills): 0.190 -> 0.154 ms per 1024 VLP-16 scans; the same bound
-// on k_segment / k_ground_elev_ransac spills and was slower
+// bits [j0, j0 + 64) of a column mask kept as 64 columns a word (the word after the last is zero)
+__device__ __forceinline__ uint64_t add_bits(const uint64_t* m, int j0) {
+  const int w = j0 >> 6, sh = j0 & 63;
+  const uint64_t lo = m[w] >> sh;
+  return sh ? lo | (m[w + 1] << (64 - sh)) : lo;
+}
+
+// Pass 1 computes both add_test results of every ground == 2 cell up front, lanes on interleaved
+// columns (j = lane + 64 k: one load instruction touches 16 consecutive lines, kU of them in flight),
+// and leaves them as two column masks in LDS; the two state scans then read LDS only. The backward
+// mask is a superset: the backward pass still tests g[j] == 2 when it visits the cell, after the
+// forward pass's promotions. 8 waves per SIMD, no spills.
 __global__ __launch_bounds__(256, 8) void k_ground_add(DevCfg c, DevBufs d) {
   __shared__ int8_t grow[4][2048];
+  __shared__ uint64_t gcand[4][2][33];  // [forward, backward] candidate masks, W <= 2048, one zero word
   const int b = blockIdx.y;
   const int wv = threadIdx.x >> 6, l = lane_id();
   const int i = blockIdx.x * 4 + wv;
@@ -574,19 +591,56 @@ __global__ __launch_bounds__(256, 8) void k_ground_add(DevCfg c, DevBufs d) {
   for (int j = l; j < W; j += 64) g[j] = d.ground[rbase + j];
   __builtin_amdgcn_wave_barrier();
   const float4* full = d.full + rbase;
-  const int CH = (W + 63) / 64;
+  const int CH = (W + 63) / 64;  // columns per lane chunk of the scans = words per mask
   const uint32_t kId = 0xE4u;  // identity map on 4 states
+  uint64_t* mf = gcand[wv][0];
+  uint64_t* mb = gcand[wv][1];
+
+  // ---- pass 1: candidate bits, forward (neighbour j - 2, j >= 2) and backward (j + 2, j <= W - 3) ----
+  {
+    constexpr int kU = 2;  // 4 spill at 64 VGPRs (3 x 3 floats per column and their addresses)
+    for (int k0 = 0; k0 < CH; k0 += kU) {
+      AddPt p[kU], pl[kU], pr[kU];
+      bool two[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int j = (k0 + u) * 64 + l;
+        two[u] = j < W && g[j] == 2;
+        if (two[u]) {
+          p[u] = add_load(full, j);
+          pl[u] = add_load(full, j >= 2 ? j - 2 : j);
+          pr[u] = add_load(full, j + 2 < W ? j + 2 : j);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int j = (k0 + u) * 64 + l;
+        bool cf = false, cb = false;
+        if (two[u]) {
+          const float r = add_norm(p[u]);
+          cf = j >= 2 && add_test(p[u], r, pl[u]);
+          cb = j + 2 < W && add_test(p[u], r, pr[u]);
+        }
+        const uint64_t wf = __ballot(cf), wb = __ballot(cb);
+        if (l == 0 && k0 + u < CH) {
+          mf[k0 + u] = wf;
+          mb[k0 + u] = wb;
+        }
+      }
+    }
+    if (l == 0) mf[CH] = mb[CH] = 0;
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (c.dbg_phase <= 0) return;
 
   // ---- forward pass, j = 2 .. W-1 ----
   {
     const int j0 = l * CH, j1 = min(j0 + CH, W);
+    const uint64_t candBits = j0 < W ? add_bits(mf, j0) : 0;  // bit j - j0; CH <= 32
     uint32_t F = kId;
-    uint64_t candBits = 0;  // CH <= 64
     for (int j = j0; j < j1; ++j) {
       if (j < 2) continue;
-      const bool two = g[j] == 2;
-      const bool cand = two && add_test(full, j, j - 2);
-      if (cand) candBits |= 1ull << (j - j0);
+      const bool cand = (candBits >> (j - j0)) & 1ull;
       F = st_push(F, g[j] == 1, cand);
     }
     // exclusive scan of maps over lanes (lane order = column order)
@@ -611,17 +665,18 @@ __global__ __launch_bounds__(256, 8) void k_ground_add(DevCfg c, DevBufs d) {
     }
   }
   __builtin_amdgcn_wave_barrier();
+  if (c.dbg_phase <= 1) return;
   // ---- backward pass, j = W-3 .. 0, neighbours j+1, j+2 ----
   {
     // lane l owns the l-th chunk counted from the right end.
     const int hi = W - 3;  // first column visited
     const int j1 = hi - l * CH, j0 = max(j1 - CH + 1, 0);  // chunk [j0, j1], visited descending
+    const uint64_t candBits = j1 >= 0 ? add_bits(mb, j0) : 0;  // bit j - j0
     uint32_t F = kId;
-    uint64_t candBits = 0;
+    uint64_t live = 0;  // candidates still 2 after the forward pass
     for (int j = j1; j >= j0; --j) {
-      const bool two = g[j] == 2;
-      const bool cand = two && add_test(full, j, j + 2);
-      if (cand) candBits |= 1ull << (j1 - j);
+      const bool cand = ((candBits >> (j - j0)) & 1ull) && g[j] == 2;
+      if (cand) live |= 1ull << (j - j0);
       F = st_push(F, g[j] == 1, cand);
     }
     uint32_t incl = F;
@@ -636,7 +691,7 @@ __global__ __launch_bounds__(256, 8) void k_ground_add(DevCfg c, DevBufs d) {
     uint32_t s = st_apply(excl, s0);
     __builtin_amdgcn_wave_barrier();
     for (int j = j1; j >= j0; --j) {
-      const bool cand = (candBits >> (j1 - j)) & 1ull;
+      const bool cand = (live >> (j - j0)) & 1ull;
       const uint32_t a = s & 1u, bb = s >> 1;
       bool one = g[j] == 1;
       if (cand && (a | bb)) { g[j] = 1; one = true; }
@@ -1001,43 +1056,48 @@ __global__ __launch_bounds__(1024) void k_label(DevCfg c, DevBufs d) {
   if constexpr (kLds) {
     // label_mat init (IP:752-759): -1 for ground or empty, else 0 -> union-find singleton; and the
     // BFS edge test of every cell with its right (wrapping, IP:884-886) and lower neighbour as two
-    // bits in LDS (ebits, after the parent words), from ranges loaded kE cells per lane at once —
-    // the union pass then reads LDS only (its global loads sat behind data-dependent branches)
+    // bits in LDS (ebits, after the parent words) — the union pass then reads LDS only (its global
+    // loads sat behind data-dependent branches). A wave takes a block of 64 columns, a lane the
+    // H <= 16 rows of one column, all loads in flight together: every range is read once, the lower
+    // neighbour is the lane's next register and the right neighbour the next lane's value; only the
+    // column after the block (column 0 after the last: the wrap) is read again, a row per lane.
     uint8_t* ebits = reinterpret_cast<uint8_t*>(lds_parent + HW);
-    constexpr int kE = 4;
-    for (int t0 = 0; t0 < HW; t0 += kE * nt) {
-      float r[kE], rr[kE], rd[kE];
-      int8_t gv[kE];
+    constexpr int kH = 16;  // ccl_lds: H <= 16
+    const int ln = lane_id();
+    for (int j0 = (tid >> 6) * 64; j0 < W; j0 += nt) {
+      const int j = j0 + ln;
+      const bool in = j < W;
+      const int jc = in ? j : W - 1, rows = in ? H : 0;
+      float r[kH];
+      int8_t gv[kH];
 #pragma unroll
-      for (int u = 0; u < kE; ++u) {
-        const int cell = t0 + u * nt + tid;
-        if (cell >= HW) continue;
-        const int i = cell / W, j = cell - i * W;
-        gv[u] = g[cell];
-        r[u] = rng[cell];
-        rr[u] = rng[(j + 1 < W) ? cell + 1 : cell + 1 - W];
-        rd[u] = i + 1 < H ? rng[cell + W] : FLT_MAX;
+      for (int i = 0; i < kH; ++i) {  // (clamped, not predicated: cells outside are never used)
+        const int q = (i < H ? i : H - 1) * W + jc;
+        r[i] = rng[q];
+        gv[i] = g[q];
       }
-      // A wave holds 64 consecutive cells of slot u: the right edges between neighbours of one row
-      // inside the wave are resolved here, each cell pointing straight at the first cell of its
-      // linked run (the run's smallest index, so the union-find invariant "root = smallest cell"
-      // holds); only the wave's last right edge, the row wrap and the down edges are left for the
-      // union pass.
-      const int ln = lane_id();
+      const float rx = ln < H ? rng[ln * W + (j0 + 64 < W ? j0 + 64 : 0)] : FLT_MAX;
+      // A wave holds 64 consecutive cells of row i: the right edges between neighbours inside the
+      // wave are resolved here, each cell pointing straight at the first cell of its linked run (the
+      // run's smallest index, so the union-find invariant "root = smallest cell" holds); only the
+      // wave's last right edge, the row wrap and the down edges are left for the union pass.
 #pragma unroll
-      for (int u = 0; u < kE; ++u) {
-        const int cell = t0 + u * nt + tid;
-        const bool in = cell < HW;
-        const int i = in ? cell / W : 0, j = in ? cell - i * W : 0;
-        const bool l0 = in && !(gv[u] == 1 || r[u] == FLT_MAX);
-        const bool er = in && seg_edge(c, r[u], rr[u], true);
-        const bool ed = in && i + 1 < H && seg_edge(c, r[u], rd[u], false);
+      for (int i = 0; i < kH; ++i) {
+        // (rows as a per-lane value: uniform tests of i against H would be hoisted out of the block
+        // loop as 32 lane masks, more scalar registers than there are)
+        const bool live = i < rows;
+        const int cell = i * W + j;
+        const float rn = __shfl_down(r[i], 1, 64), rw = __shfl(rx, i, 64);
+        const float rr = (ln == 63 || j + 1 >= W) ? rw : rn;
+        const bool l0 = live && !(gv[i] == 1 || r[i] == FLT_MAX);
+        const bool er = live && seg_edge(c, r[i], rr, true);
+        const bool ed = i + 1 < rows && seg_edge(c, r[i], i + 1 < kH ? r[i + 1] : FLT_MAX, false);
         const bool l0n = __shfl_down(l0 ? 1 : 0, 1, 64) != 0;  // the next lane's cell (j + 1 if j + 1 < W)
         const bool link = er && l0 && l0n && ln < 63 && j + 1 < W;  // resolved in the wave
         const unsigned long long lk = __ballot(link);
         const unsigned long long heads = ~(lk << 1);                 // lane 0 always starts a run
         const int head = 63 - __clzll((long long)(heads & ((2ull << ln) - 1ull)));
-        if (!in) continue;
+        if (!live) continue;
         P.st(cell, l0 ? cell - (ln - head) : -1);
         ebits[cell] = (uint8_t)((er && !link ? 1 : 0) | (ed ? 2 : 0));
       }
@@ -1126,24 +1186,32 @@ __global__ __launch_bounds__(1024) void k_label(DevCfg c, DevBufs d) {
     // Everything stays in the LDS word of each cell: -1 = not label 0; a member holds its root's
     // index (>= 0); a root holds 0x80000000 | size << 16 | row mask of its pushed members (size <=
     // HW <= 32000 keeps the word != -1), later 0x80000000 | label. Global memory sees the labels once.
-    // read-only walks: the only stores are P[cell] = its root, so every word a concurrent walk
-    // reads is still an ancestor (path halving here could store a stale grandparent over a root)
+    // read-only walks: the only stores are a cell's own word, a member's = its root, a root's = its
+    // first stats word (size 1, no rows), so every word a concurrent walk reads is still an ancestor
+    // or tells that the cell it sits in is a root (path halving here could store a stale
+    // grandparent over a root)
     for (int cell = tid; cell < HW; cell += nt) {
       int x = P.ld(cell);
       if (x < 0) continue;
-      for (int px = P.ld(x); px != x; px = P.ld(x)) x = px;
-      P.st(cell, x);
+      for (int px = P.ld(x); px != x && px >= 0; px = P.ld(x)) x = px;
+      P.st(cell, x == cell ? (int)(0x80000000u | (1u << 16)) : x);
     }
     __syncthreads();
     if (c.dbg_phase <= 2) return;
-    for (int cell = tid; cell < HW; cell += nt)
-      if (P.ld(cell) == cell) P.st(cell, (int)(0x80000000u | (1u << 16)));
-    __syncthreads();
-    for (int cell = tid; cell < HW; cell += nt) {
-      const int root = P.ld(cell);
-      if (root < 0) continue;
-      atomicAdd(&lds_parent[root], 1 << 16);
-      atomicOr(&lds_parent[root], 1 << (cell / W));
+    // A wave holds 64 consecutive cells: neighbouring lanes of one row with the same root are a run,
+    // and only its first lane adds the run's length and the row bit to the root's word.
+    for (int c0 = 0; c0 < HW; c0 += nt) {
+      const int cell = c0 + tid, ln = lane_id();
+      const int root = cell < HW ? P.ld(cell) : -1;
+      const int row = cell / W;
+      const int rootp = __shfl_up(root, 1, 64), rowp = __shfl_up(row, 1, 64);
+      const bool member = root >= 0;
+      const bool first = member && (ln == 0 || rootp != root || rowp != row);
+      const unsigned long long ends = (__ballot(first) | ~__ballot(member)) & ~((2ull << ln) - 1ull);
+      if (!first) continue;
+      const int len = (ends ? __ffsll((long long)ends) - 1 : 64) - ln;
+      atomicAdd(&lds_parent[root], len << 16);
+      atomicOr(&lds_parent[root], 1 << row);
     }
     __syncthreads();
     if (c.dbg_phase <= 3) return;
