@@ -887,6 +887,90 @@ int32_t llsr_mapping_associate(const float transform_sum_fa[6], const float tran
                                const float transform_aft_mapped[6], float transform_sum[6],
                                float transform_tobe_mapped[6], float transform_incre[6]);
 
+/* ---- Prior map: localising in a saved map ----
+ * The reference saves cornerMap / surfaceMap (saveMapService) and has no way to take them back: its
+ * /initialpose subscriber's body is commented out (MO:437-456). A prior map holds one static corner
+ * and one static surf cloud (float4 x, y, z, intensity in the map frame, as the save calls above write
+ * them; never downsampled here) and crops both around P positions in one call; attached to a mapping
+ * handle, the crop takes the place of extractSurroundingKeyFrames for every slot.
+ * Stored order, per kind: tile coordinate i = (int)floorf(c / tile) - min over the cloud, per axis
+ * (one correctly rounded float32 divide); key = (iz ny + iy) nx + ix; the cloud stably sorted by key,
+ * with tile_start[ntiles + 1] over the keys. The crop of a kind at a position is exactly the stored
+ * points with d^2 = ((0 + dx^2) + dy^2) + dz^2 < float(double(radius) * double(radius)) in float32, in
+ * stored order (the predicate of the global map's step 2). Tiles that cannot hold such a point are
+ * skipped; no point is copied untested.
+ * hip_device == LLSR_PRIOR_HOST: no device; the same index and the same crop run serially over heap
+ * buffers, `out` is host memory, and every result is bit for bit the device's. One call at a time per
+ * object. */
+#define LLSR_PRIOR_HOST (-1)
+#define LLSR_PRIOR_CORNER 0
+#define LLSR_PRIOR_SURF 1
+typedef struct llsr_prior llsr_prior;
+typedef struct llsr_prior_config {
+  float radius;   /* surrounding_keyframe_search_radius, 50 (CFG:26) */
+  float tile;     /* tile edge, 10 m */
+} llsr_prior_config;
+typedef struct llsr_prior_report {
+  int64_t n_points[2];      /* [kind]: corner, surf */
+  int64_t n_tiles[2];       /* nx ny nz */
+  int64_t n_tiles_used[2];  /* tiles that hold a point */
+  int32_t dims[2][3];       /* nx, ny, nz */
+  int32_t origin[2][3];     /* min over the cloud of floorf(c / tile), per axis */
+  float radius, tile;
+  int32_t device;           /* LLSR_PRIOR_HOST or the HIP device */
+  int32_t pad;
+} llsr_prior_report;
+int32_t llsr_prior_config_default(llsr_prior_config* cfg);
+/* cfg NULL: the defaults. NULL: a radius or tile that is not finite and positive, no such device, no
+ * memory. */
+llsr_prior* llsr_prior_create(const llsr_prior_config* cfg, int32_t hip_device);
+void llsr_prior_destroy(llsr_prior* p);
+const char* llsr_prior_last_error(const llsr_prior* p);
+/* Replace both clouds (host arrays, [n][4] floats; an empty kind is allowed). The index is built on the
+ * host, once per map. LLSR_EINVAL: a non-finite coordinate; LLSR_ERANGE: more than 2^24 tiles or 2^31 - 2
+ * points of one kind, or a tile index beyond +-2^30 (the error text names a tile size that fits). A
+ * refused call leaves the object as it was. Synchronises hip_stream (NULL: the object's own). */
+int32_t llsr_prior_load(llsr_prior* p, const float* corner, int64_t n_corner, const float* surf, int64_t n_surf,
+                        void* hip_stream);
+int32_t llsr_prior_info(const llsr_prior* p, llsr_prior_report* out);
+/* Kind `kind`'s cloud in stored order into out_host[4 * cap] / its tile_start into out_host[cap];
+ * they return the point count / ntiles + 1 (may exceed cap; negative: an error). */
+int64_t llsr_prior_points(const llsr_prior* p, int32_t kind, float* out_host, int64_t cap);
+int64_t llsr_prior_tile_starts(const llsr_prior* p, int32_t kind, uint32_t* out_host, int64_t cap);
+/* The crops around positions3 (host, [P][3]): `out` (device float4, 16-byte aligned; host memory on
+ * a host object; capacity `cap` points) receives the P corner crops packed, then the P surf crops;
+ * corner_off / surf_off (host, [P + 1] each) are offsets in points into `out`: position p's corner
+ * crop is points corner_off[p] .. corner_off[p + 1] - 1, corner_off[0] = 0, surf_off[0] =
+ * corner_off[P]. This is the map side of llsr_s2m_batch: one buffer, two offset rows. A position with
+ * a non-finite coordinate gets empty crops. out NULL with cap 0 only counts. When cap is too small the
+ * call returns LLSR_ERANGE with the sizes in the offsets and nothing written, and a retry with a
+ * larger buffer gives the identical result. LLSR_ERANGE also for P outside [1, 32767]. On the device:
+ * a counting kernel over (row of tiles, position, kind), a scan per position, one copy of the 2 P
+ * totals to the host, a writing kernel. Synchronises hip_stream (NULL: the object's own). */
+int32_t llsr_prior_crop_batch(llsr_prior* p, const float* positions3, int32_t P, float* out, int64_t cap,
+                              int64_t* corner_off, int64_t* surf_off, void* hip_stream);
+/* Diagnostic: the last crop on p — its device time in ms (HIP events around both kernels; wall time
+ * on the host), the points the predicate ran on and the points written. */
+int32_t llsr_prior_last_crop(const llsr_prior* p, float* ms, int64_t* tested, int64_t* written);
+/* The mapping chain in localisation mode. llsr_mapping_set_prior attaches p (on the handle's device;
+ * not owned: it must outlive the attachment; NULL detaches) to every slot. Allowed only directly after
+ * llsr_mapping_init or llsr_mapping_reset, before any frame, else LLSR_EINVAL; the reset keeps the
+ * attachment, the init drops it. With a prior attached MapOptimization::run differs in three things:
+ * extractSurroundingKeyFrames is one crop over all stepping slots at their currentRobotPosPoint,
+ * handed straight to the scan-to-map batch (the empty-store return of MO:1097 does not apply: a slot
+ * has a local map from its first MapOptimization frame); saveKeyFramesAndFactor records the key pose,
+ * its time and the pose-graph factor but no clouds; and the first-keyframe distinction counts key
+ * poses. llsr_mapping_slot.map then reports the crop sizes in n_corner_map = n_corner_ds and
+ * n_surf_map = n_surf_ds, its other fields zero. The calls that need keyframe clouds — the global map
+ * and save calls and both loop-closure calls of the chain — return LLSR_ENOSYS.
+ * llsr_mapping_set_pose is the /initialpose handler the reference left commented out: between batches,
+ * slot b's transformAftMapped, transformTobeMapped and transformLast become pose6 (transform_aft_mapped's
+ * layout) and currentRobotPosPoint its position; transformBefMapped stays, so the next
+ * transformAssociateToMap carries the pose forward by the odometry since the last mapped frame. With
+ * or without a prior. */
+int32_t llsr_mapping_set_prior(llsr_handle* h, llsr_prior* p);
+int32_t llsr_mapping_set_pose(llsr_handle* h, int32_t b, const float pose6[6]);
+
 
 /* ---- FA end of scan on the FA node's thread (host side, no handle) ----
  * For a node whose FeatureAssociation thread owns its own clouds and calls llsr_scan2scan on its

@@ -14,6 +14,7 @@
 #include "llsr_handle.h"
 #include "llsr_icp.h"
 #include "llsr_pg.h"
+#include "llsr_prior_internal.h"
 
 namespace llsr {
 // adjustOutlierCloud (FA:2600-2610): the IP outlier cloud of slot b (d.outl, [B][HW]) with
@@ -59,6 +60,7 @@ extern "C" int32_t llsr_mapping_reset(llsr_handle* h) {
   }
   mp.times.clear();
   mp.times_staged = false;
+  mp.fresh = true;  // (the attached prior map stays)
   if (mp.pg) llsr_pg_reset(mp.pg, -1);
   const int B = (int)mp.slot.size();
   HIP_OK(h, hipMemset(mp.sm.d_deg, 0, sizeof(int) * B));      // isDegenerate = false (MO:285)
@@ -79,6 +81,7 @@ void mapping_free(llsr_handle* h) {
   if (mp.pg) llsr_pg_destroy(mp.pg);
   mp.pg = nullptr;
   mp.sm = llsr_handle::MapSmall{};
+  mp.prior = nullptr;  // llsr_mapping_init drops the attachment
   mp.live = false;
 }
 
@@ -232,6 +235,8 @@ static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::v
   if (rc != LLSR_OK) return fail(h, rc, std::string("downsample: ") + llsr_map_last_error(mp.vg));
   // extractSurroundingKeyFrames (MO:1096-1232) around currentRobotPosPoint, every slot with
   // keyframes in one pass (a slot without keyframes keeps an empty local map, MO:1097)
+  // With a prior map attached: its crop around the same point, for every stepping slot, keyframes
+  // or not
   std::vector<llsr_map*> emaps;
   std::vector<int> eslot;
   std::vector<float> epos;
@@ -241,7 +246,7 @@ static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::v
     sl.mrep = llsr_map_report{};
     sl.n_cq = (int)(dso[3 * NB + b + 1] - dso[3 * NB + b]);
     sl.n_sq = (int)(toto[b + 1] - toto[b]);
-    if (llsr_map_num_keyframes(sl.map) == 0) continue;
+    if (!mp.prior && llsr_map_num_keyframes(sl.map) == 0) continue;
     emaps.push_back(sl.map);
     eslot.push_back(b);
     epos.insert(epos.end(), sl.robot, sl.robot + 3);
@@ -250,7 +255,24 @@ static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::v
   std::vector<llsr_map_report> ereps(nE > 0 ? nE : 1);
   std::vector<long long> eoc(nE + 1, 0), eos(nE + 1, 0);
   const float4* lmap = nullptr;
-  if (nE > 0) {
+  if (nE > 0 && mp.prior) {
+    std::vector<int64_t> oc(nE + 1), os(nE + 1);
+    rc = llsr_prior_ns::crop_begin(mp.prior, epos.data(), nE, oc.data(), os.data(), s);
+    if (rc != LLSR_OK) return fail(h, rc, std::string("prior crop: ") + llsr_prior_ns::error_of(mp.prior));
+    rc = mp_grow(h, mp.cmap, (size_t)os[nE] + 1, 0, s);
+    if (rc != LLSR_OK) return rc;
+    rc = llsr_prior_ns::crop_write(mp.prior, (float*)mp.cmap.p(), os[nE], s);
+    if (rc != LLSR_OK) return fail(h, rc, std::string("prior crop: ") + llsr_prior_ns::error_of(mp.prior));
+    lmap = mp.cmap.p();
+    for (int e = 0; e <= nE; ++e) {
+      eoc[e] = oc[e];
+      eos[e] = os[e];
+    }
+    for (int e = 0; e < nE; ++e) {  // the crop is the local map as it is: no VoxelGrid (…Map = …DS)
+      ereps[e].n_corner_map = ereps[e].n_corner_ds = oc[e + 1] - oc[e];
+      ereps[e].n_surf_map = ereps[e].n_surf_ds = os[e + 1] - os[e];
+    }
+  } else if (nE > 0) {
     rc = llsr_mapping::extract_multi(mp.vg, emaps.data(), nE, epos.data(), ereps.data(), &lmap, eoc.data(),
                                      eos.data(), s);
     if (rc != LLSR_OK) return fail(h, rc, std::string("extract: ") + llsr_map_last_error(mp.vg));
@@ -332,7 +354,9 @@ static int32_t mapping_mo(llsr_handle* h, int32_t B, hipStream_t s, const std::v
       P.transformLast[k] = est[k];
       if (!first) P.transformTobeMapped[k] = P.transformAftMapped[k];
     }
-    const int kf = llsr_map_add_keyframe(
+    // (localisation: the key pose and its time only; the store then counts key poses, no clouds)
+    const int kf = mp.prior ? llsr_map_add_keyframe(sl.map, kp, nullptr, 0, nullptr, 0, nullptr, 0, s)
+                            : llsr_map_add_keyframe(
         sl.map, kp, (const float*)(o.scan_c + hs[b]), (int32_t)(hs[b + 1] - hs[b]),
         (const float*)(mp.ds.p() + dso[NB + 2 * b]), (int32_t)(dso[NB + 2 * b + 1] - dso[NB + 2 * b]),
         (const float*)(mp.ds.p() + dso[NB + 2 * b + 1]), (int32_t)(dso[NB + 2 * b + 2] - dso[NB + 2 * b + 1]), s);
@@ -366,6 +390,7 @@ static int32_t mapping_batch(llsr_handle* h, const float* d_xyzi, const int64_t*
     return fail(h, LLSR_EINVAL, "the staged scan times (llsr_mapping_stage_times) are for another batch size");
   hipStream_t s;
   HIP_OK(h, enter(h, hip_stream, &s));
+  mp.fresh = false;
   int32_t rc = odo_batch(h, d_xyzi, d_offsets, B, samples, overwrite, s);
   if (rc != LLSR_OK) return rc;
   // the staged scan times are consumed here, with the odometry's advance
@@ -486,6 +511,8 @@ extern "C" int32_t llsr_mapping_fetch(llsr_handle* h, int32_t b, llsr_mapping_sl
   return LLSR_OK;
 }
 
+static const char kNoClouds[] = "a prior map is attached (llsr_mapping_set_prior): the slots keep no keyframe clouds";
+
 // publishGlobalMap / saveMapService on slot b's store (llsr_map.hip), after the handle's own streams
 static int32_t mapping_slot_map(llsr_handle* h, int32_t b, llsr_handle::MapSlot** sl) {
   auto& mp = h->mp;
@@ -502,6 +529,7 @@ extern "C" int32_t llsr_mapping_global_map(llsr_handle* h, int32_t b, const llsr
                                            float* d_planar, int64_t cap_planar, llsr_global_map_report* rep,
                                            void* hip_stream) {
   if (!h || !rep) return LLSR_EINVAL;
+  if (h->mp.live && h->mp.prior) return fail(h, LLSR_ENOSYS, kNoClouds);
   llsr_handle::MapSlot* sl = nullptr;
   int32_t rc = mapping_slot_map(h, b, &sl);
   if (rc != LLSR_OK) return rc;
@@ -514,6 +542,7 @@ extern "C" int32_t llsr_mapping_save_map(llsr_handle* h, int32_t b, float* d_cor
                                          float* d_surf, int64_t cap_surf, int64_t* n_corner, int64_t* n_surf,
                                          void* hip_stream) {
   if (!h) return LLSR_EINVAL;
+  if (h->mp.live && h->mp.prior) return fail(h, LLSR_ENOSYS, kNoClouds);
   llsr_handle::MapSlot* sl = nullptr;
   int32_t rc = mapping_slot_map(h, b, &sl);
   if (rc != LLSR_OK) return rc;
@@ -558,6 +587,7 @@ extern "C" int32_t llsr_mapping_loop_closure(llsr_handle* h, const llsr_loop_con
   if (!h || !reps) return LLSR_EINVAL;
   auto& mp = h->mp;
   if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (mp.prior) return fail(h, LLSR_ENOSYS, kNoClouds);
   if (B < 1 || B > (int)mp.slot.size()) return fail(h, LLSR_ERANGE, "batch size outside [1, max_batch]");
   llsr_loop_config own;
   if (!cfg) {  // the block of the handle's lidar, chosen as llsr_mapping_init chooses the map's
@@ -637,6 +667,34 @@ extern "C" int32_t llsr_mapping_set_key_poses(llsr_handle* h, int32_t b, const f
   return LLSR_OK;
 }
 
+// ---- localisation in a prior map ----
+extern "C" int32_t llsr_mapping_set_prior(llsr_handle* h, llsr_prior* p) {
+  if (!h) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (!mp.fresh)
+    return fail(h, LLSR_EINVAL, "llsr_mapping_set_prior: allowed only directly after llsr_mapping_init or "
+                                "llsr_mapping_reset, before any frame");
+  if (p && llsr_prior_ns::device_of(p) != h->device)
+    return fail(h, LLSR_EINVAL, "llsr_mapping_set_prior: the prior map is not on the handle's device");
+  mp.prior = p;
+  return LLSR_OK;
+}
+
+// The /initialpose handler the reference left commented out (MO:437-456)
+extern "C" int32_t llsr_mapping_set_pose(llsr_handle* h, int32_t b, const float pose6[6]) {
+  if (!h) return LLSR_EINVAL;
+  auto& mp = h->mp;
+  if (!mp.live) return fail(h, LLSR_EINVAL, "llsr_mapping_init not called");
+  if (!pose6) return fail(h, LLSR_EINVAL, "llsr_mapping_set_pose: pose6 is NULL");
+  if (b < 0 || b >= (int)mp.slot.size()) return fail(h, LLSR_ERANGE, "slot outside [0, max_batch)");
+  auto& sl = mp.slot[b];
+  for (int k = 0; k < 6; ++k)
+    sl.pose.transformAftMapped[k] = sl.pose.transformTobeMapped[k] = sl.pose.transformLast[k] = pose6[k];
+  for (int k = 0; k < 3; ++k) sl.robot[k] = pose6[3 + k];
+  return LLSR_OK;
+}
+
 // ---- the slots' pose graphs: the factor graph of MO:1086-1090 / 1612-1690 per slot ----
 extern "C" int32_t llsr_mapping_enable_pose_graph(llsr_handle* h, int32_t on, int32_t max_loops) {
   if (!h) return LLSR_EINVAL;
@@ -679,6 +737,7 @@ extern "C" int32_t llsr_mapping_close_loops(llsr_handle* h, const llsr_loop_conf
                                             llsr_pg_report* pg_reps, void* hip_stream) {
   if (!h || !loop_reps) return LLSR_EINVAL;
   auto& mp = h->mp;
+  if (mp.live && mp.prior) return fail(h, LLSR_ENOSYS, kNoClouds);
   if (!mp.live || !mp.pg) return fail(h, LLSR_EINVAL, "llsr_mapping_enable_pose_graph not called");
   int32_t rc = llsr_mapping_loop_closure(h, loop_cfg, B, loop_reps, hip_stream);
   if (rc != LLSR_OK) return rc;

@@ -176,6 +176,10 @@ struct LLSR_HIDDEN llsr_handle {
     llsr_icp* icp = nullptr;
     // the slots' pose graphs (llsr_mapping_enable_pose_graph): one object, graph b = slot b; NULL = off
     llsr_pg* pg = nullptr;
+    // localisation mode (llsr_mapping_set_prior): the attached prior map, not owned; NULL = mapping.
+    // `fresh`: no frame since llsr_mapping_init / llsr_mapping_reset (when attaching is allowed)
+    llsr_prior* prior = nullptr;
+    bool fresh = false;
   } mp;
   // IMU de-skew (llsr_stage_imu): device windows + per-slot carry and their pinned staging, allocated
   // on the first staging call; `armed` until a batch's feature stage consumes it

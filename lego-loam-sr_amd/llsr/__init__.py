@@ -60,6 +60,9 @@ EXPORTS = [
     "llsr_imu_init", "llsr_imu_callback", "llsr_imu_scan_window", "llsr_imu_deskew_host", "llsr_stage_imu",
     "llsr_fetch_imu_report", "llsr_set_imu_undistortion", "llsr_integrate_transformation_imu",
     "llsr_transform_to_end_imu", "llsr_first_scan_imu",
+    "llsr_prior_config_default", "llsr_prior_create", "llsr_prior_destroy", "llsr_prior_last_error",
+    "llsr_prior_load", "llsr_prior_info", "llsr_prior_points", "llsr_prior_tile_starts", "llsr_prior_crop_batch",
+    "llsr_prior_last_crop", "llsr_mapping_set_prior", "llsr_mapping_set_pose",
 ]
 
 
@@ -212,6 +215,20 @@ def lib():
         L.llsr_mapping_close_loops.argtypes = [C.c_void_p, C.POINTER(_abi.LoopConfig), C.POINTER(_abi.PgConfig),
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.llsr_mapping_pose_graph_poses.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.llsr_prior_config_default.argtypes = [C.POINTER(_abi.PriorConfig)]
+        L.llsr_prior_create.argtypes = [C.POINTER(_abi.PriorConfig), C.c_int32]
+        L.llsr_prior_destroy.argtypes = [C.c_void_p]
+        L.llsr_prior_last_error.argtypes = [C.c_void_p]
+        L.llsr_prior_load.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        L.llsr_prior_info.argtypes = [C.c_void_p, C.POINTER(_abi.PriorReport)]
+        L.llsr_prior_points.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+        L.llsr_prior_tile_starts.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+        L.llsr_prior_crop_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+        L.llsr_prior_last_crop.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64)]
+        L.llsr_mapping_set_prior.argtypes = [C.c_void_p, C.c_void_p]
+        L.llsr_mapping_set_pose.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         _loop = [C.POINTER(_abi.LoopConfig), C.c_void_p, C.c_double, C.POINTER(_abi.LoopReport)]
         L.llsr_map_loop_submaps.argtypes = [C.c_void_p] + _loop + [C.c_void_p, C.c_int64] * 4 + [C.c_void_p]
         L.llsr_map_loop_closure.argtypes = [C.c_void_p, C.c_void_p] + _loop + [C.c_void_p, C.c_int64] * 2 + [C.c_void_p]
@@ -232,8 +249,14 @@ def lib():
             if fn not in ("llsr_last_error", "llsr_kernel_name", "llsr_destroy", "llsr_map_create",
                           "llsr_map_destroy", "llsr_map_last_error", "llsr_build_id", "llsr_icp_create",
                           "llsr_icp_destroy", "llsr_icp_last_error", "llsr_pg_create", "llsr_pg_destroy",
-                          "llsr_pg_last_error"):
+                          "llsr_pg_last_error", "llsr_prior_create", "llsr_prior_destroy", "llsr_prior_last_error",
+                          "llsr_prior_points", "llsr_prior_tile_starts"):
                 getattr(L, fn).restype = C.c_int32
+        L.llsr_prior_create.restype = C.c_void_p
+        L.llsr_prior_destroy.restype = None
+        L.llsr_prior_last_error.restype = C.c_char_p
+        L.llsr_prior_points.restype = C.c_int64
+        L.llsr_prior_tile_starts.restype = C.c_int64
         L.llsr_destroy.restype = None
         L.llsr_map_create.restype = C.c_void_p
         L.llsr_map_destroy.restype = None
@@ -286,7 +309,9 @@ class Pipeline:
 
     def _check(self, rc, what):
         if rc != 0:
-            raise LlsrError(f"{what} failed ({rc}): {lib().llsr_last_error(self._h).decode()}")
+            e = LlsrError(f"{what} failed ({rc}): {lib().llsr_last_error(self._h).decode()}")
+            e.code = rc
+            raise e
 
     def reset(self):
         self._check(lib().llsr_reset_state(self._h), "llsr_reset_state")
@@ -624,6 +649,19 @@ class Pipeline:
                                                      None if e is None else e.ctypes.data),
                     "llsr_mapping_set_key_poses")
 
+
+    def mapping_set_prior(self, prior: "PriorMap | None"):
+        """Localisation mode (llsr_mapping_set_prior): every slot's local map becomes the crop of
+        `prior` (a PriorMap on this device; None detaches). Only directly after mapping_init or
+        mapping_reset. The Pipeline keeps a reference: the prior outlives the attachment."""
+        self._check(lib().llsr_mapping_set_prior(self._h, prior._w if prior is not None else None),
+                    "llsr_mapping_set_prior")
+        self._prior = prior
+
+    def mapping_set_pose(self, b: int, pose6):
+        """The /initialpose of slot b (llsr_mapping_set_pose): pose6 in transform_aft_mapped's layout."""
+        p = np.ascontiguousarray(pose6, np.float32).reshape(6)
+        self._check(lib().llsr_mapping_set_pose(self._h, b, p.ctypes.data), "llsr_mapping_set_pose")
 
     def mapping_enable_pose_graph(self, on: bool = True, max_loops: int = 16):
         """Keep a pose graph per slot (llsr_mapping_enable_pose_graph): every keyframe a slot saves from
@@ -1122,6 +1160,130 @@ class PoseGraph:
         out = np.zeros((max(n, 1), 6), np.float32)
         lib().llsr_pg_poses(self._w, p, out.ctypes.data, n)
         return out[:n].copy()
+
+
+class PriorMap:
+    """A saved map to localise in (llsr_prior, include/llsr.h): a static corner and a
+    static surf cloud in tile order, cropped around P positions per call. device None builds the host
+    twin (LLSR_PRIOR_HOST), whose crops are numpy arrays; on a device they are torch CUDA tensors."""
+
+    KINDS = ("corner", "surf")
+
+    def __init__(self, radius: float | None = None, tile: float | None = None, device: int | None = 0):
+        c = _abi.PriorConfig()
+        lib().llsr_prior_config_default(C.byref(c))
+        if radius is not None:
+            c.radius = radius
+        if tile is not None:
+            c.tile = tile
+        self.device = device
+        self._w = lib().llsr_prior_create(C.byref(c), _abi.LLSR_PRIOR_HOST if device is None else device)
+        if not self._w:
+            e = LlsrError("llsr_prior_create failed: a radius or tile that is not finite and positive, "
+                          "no HIP device or no memory")
+            e.code = _abi.LLSR_EINVAL
+            raise e
+
+    @classmethod
+    def from_saved(cls, corner, surf, corner_leaf: float | None = 0.2, radius: float | None = None,
+                   tile: float | None = None, device: int | None = 0) -> "PriorMap":
+        """From saveMapService's clouds (Pipeline.mapping_save_map, LocalMap.save_map): surfaceMap is
+        already a VoxelGrid of the surf leaf; cornerMap is raw, so it goes through the VoxelGrid at
+        corner_leaf first (on device 0 for a host object; None or 0 loads it as it is)."""
+        def host(a):
+            return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, np.float32).reshape(-1, 4)
+        if corner_leaf and len(corner):
+            vg = LocalMap(0 if device is None else device)
+            corner = vg.voxel_grid([corner], [corner_leaf])[0]
+            vg.close()
+        m = cls(radius, tile, device)
+        m.load(host(corner), host(surf))
+        return m
+
+    def close(self):
+        if getattr(self, "_w", None):
+            lib().llsr_prior_destroy(self._w)
+            self._w = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc: int, what: str):
+        if rc < 0:
+            e = LlsrError(f"{what} failed ({rc}): {lib().llsr_prior_last_error(self._w).decode()}")
+            e.code = rc
+            raise e
+        return rc
+
+    def load(self, corner, surf, stream: int = 0):
+        c, s = (np.ascontiguousarray(a, np.float32).reshape(-1, 4) for a in (corner, surf))
+        self._check(lib().llsr_prior_load(self._w, c.ctypes.data, len(c), s.ctypes.data, len(s), C.c_void_p(stream)),
+                    "llsr_prior_load")
+
+    def info(self) -> dict:
+        r = _abi.PriorReport()
+        self._check(lib().llsr_prior_info(self._w, C.byref(r)), "llsr_prior_info")
+        d = {"radius": float(r.radius), "tile": float(r.tile), "device": int(r.device)}
+        for k, name in enumerate(self.KINDS):
+            d[name] = {"n_points": int(r.n_points[k]), "n_tiles": int(r.n_tiles[k]),
+                       "n_tiles_used": int(r.n_tiles_used[k]), "dims": tuple(r.dims[k][:]),
+                       "origin": tuple(r.origin[k][:])}
+        return d
+
+    def points(self, kind: int | str) -> np.ndarray:
+        """The kind's cloud in stored order."""
+        k = self.KINDS.index(kind) if isinstance(kind, str) else kind
+        n = self._check(lib().llsr_prior_points(self._w, k, None, 0), "llsr_prior_points")
+        out = np.zeros((max(n, 1), 4), np.float32)
+        lib().llsr_prior_points(self._w, k, out.ctypes.data, n)
+        return out[:n].copy()
+
+    def tile_starts(self, kind: int | str) -> np.ndarray:
+        """The kind's CSR over the tile keys, [ntiles + 1]."""
+        k = self.KINDS.index(kind) if isinstance(kind, str) else kind
+        n = self._check(lib().llsr_prior_tile_starts(self._w, k, None, 0), "llsr_prior_tile_starts")
+        out = np.zeros(max(n, 1), np.uint32)
+        lib().llsr_prior_tile_starts(self._w, k, out.ctypes.data, n)
+        return out[:n].copy()
+
+    def crop(self, positions, cap: int | None = None, count_only: bool = False, stream: int = 0) -> dict:
+        """llsr_prior_crop_batch around positions (P, 3): {"out", "corner_off", "surf_off"}; position p's
+        corner crop is out[corner_off[p]:corner_off[p + 1]], its surf crop out[surf_off[p]:surf_off[p + 1]].
+        cap None sizes the buffer with a counting call first; a given cap that is too small raises
+        LlsrError with code LLSR_ERANGE and the offsets in its `offsets` attribute."""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        P = len(pos)
+        oc, os_ = np.zeros(P + 1, np.int64), np.zeros(P + 1, np.int64)
+
+        def call(ptr, n):
+            return lib().llsr_prior_crop_batch(self._w, pos.ctypes.data, P, C.c_void_p(ptr), n, oc.ctypes.data,
+                                               os_.ctypes.data, C.c_void_p(stream))
+        if cap is None or count_only:
+            self._check(call(None, 0), "llsr_prior_crop_batch")
+            if count_only:
+                return {"out": None, "corner_off": oc, "surf_off": os_}
+            cap = int(os_[P])
+        if self.device is None:
+            out = np.zeros((max(cap, 1), 4), np.float32)
+            ptr = out.ctypes.data
+        else:
+            import torch
+            out = torch.zeros((max(cap, 1), 4), dtype=torch.float32, device=torch.device("cuda", self.device))
+            torch.cuda.synchronize(self.device)
+            ptr = out.data_ptr()
+        rc = call(ptr, cap)
+        if rc == _abi.LLSR_ERANGE:
+            e = LlsrError(f"llsr_prior_crop_batch failed ({rc}): {lib().llsr_prior_last_error(self._w).decode()}")
+            e.code, e.offsets, e.out = rc, (oc, os_), out
+            raise e
+        self._check(rc, "llsr_prior_crop_batch")
+        return {"out": out[:int(os_[P])], "corner_off": oc, "surf_off": os_}
+
+    def last_crop(self) -> dict:
+        """Diagnostic (llsr_prior_last_crop): ms, points tested, points written of the last crop."""
+        ms, t, w = C.c_float(), C.c_int64(), C.c_int64()
+        self._check(lib().llsr_prior_last_crop(self._w, C.byref(ms), C.byref(t), C.byref(w)), "llsr_prior_last_crop")
+        return {"ms": ms.value, "tested": t.value, "written": w.value}
 
 
 class Icp:

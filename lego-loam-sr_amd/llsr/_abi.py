@@ -9,6 +9,7 @@ ABI_VERSION = 2  # LLSR_ABI_VERSION of include/llsr.h these bindings mirror (che
 LLSR_OK = 0
 LLSR_ERANGE = -34
 LLSR_EINVAL = -22
+LLSR_ENOSYS = -38
 LLSR_LIDAR_VLP16 = 0
 LLSR_LIDAR_VLP32C = 1
 LLSR_LIDAR_HDL64E = 2
@@ -390,6 +391,23 @@ class PgReport(C.Structure):
         return {"state": int(self.state), "iterations": int(self.iterations), "error_before": float(self.error_before),
                 "error_after": float(self.error_after), "poses": int(self.poses), "loops": int(self.loops),
                 "ms": float(self.ms), "moved": bool(self.moved)}
+
+
+LLSR_PRIOR_HOST = -1
+LLSR_PRIOR_CORNER = 0
+LLSR_PRIOR_SURF = 1
+
+
+class PriorConfig(C.Structure):
+    """llsr_prior_config (include/llsr.h): the crop radius and the tile edge."""
+    _fields_ = [("radius", C.c_float), ("tile", C.c_float)]
+
+
+class PriorReport(C.Structure):
+    """llsr_prior_report (include/llsr.h): sizes and tile grids of the two kinds (corner, surf)."""
+    _fields_ = [("n_points", C.c_int64 * 2), ("n_tiles", C.c_int64 * 2), ("n_tiles_used", C.c_int64 * 2),
+                ("dims", (C.c_int32 * 3) * 2), ("origin", (C.c_int32 * 3) * 2), ("radius", C.c_float),
+                ("tile", C.c_float), ("device", C.c_int32), ("pad", C.c_int32)]
 
 
 class MappingSlot(C.Structure):
