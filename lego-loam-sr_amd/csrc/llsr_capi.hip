@@ -68,9 +68,12 @@ static int row_bin_bound(const DevCfg& c) {
 
 // The fused projection keeps the winning raw index per cell in LDS (k_project_fused).
 static int fused_lds(const DevCfg& c) { return c.HW * (int)sizeof(int); }
-// k_label<true>'s dynamic LDS: the parent word and the edge-bit byte of every cell (HW <= 32000:
-// <= 160000 B)
-static int label_lds(const DevCfg& c) { return c.HW * (int)(sizeof(int) + 1); }
+// k_label<true>'s dynamic LDS: the parent word of every cell, the right-edge row mask of every
+// column (16 bits, an even count of them) and a queue of 128 cells for each of the 16 waves
+// (HW <= 32000, W <= 2048: <= 136192 B)
+static int label_lds(const DevCfg& c) {
+  return c.HW * (int)sizeof(int) + (((c.W + 1) & ~1) + 16 * 128) * (int)sizeof(unsigned short);
+}
 
 static int label_band_lds(const DevCfg& c) { return c.lbl_band * c.W * (int)sizeof(int); }
 // (a use_vlp32c handle ranks its rows first: always k_row_bins -> k_project<true> -> k_gather_column)

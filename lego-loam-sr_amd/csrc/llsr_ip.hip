@@ -1055,62 +1055,98 @@ __global__ __launch_bounds__(1024) void k_label(DevCfg c, DevBufs d) {
 
   if constexpr (kLds) {
     // label_mat init (IP:752-759): -1 for ground or empty, else 0 -> union-find singleton; and the
-    // BFS edge test of every cell with its right (wrapping, IP:884-886) and lower neighbour as two
-    // bits in LDS (ebits, after the parent words) — the union pass then reads LDS only (its global
-    // loads sat behind data-dependent branches). A wave takes a block of 64 columns, a lane the
-    // H <= 16 rows of one column, all loads in flight together: every range is read once, the lower
-    // neighbour is the lane's next register and the right neighbour the next lane's value; only the
-    // column after the block (column 0 after the last: the wrap) is read again, a row per lane.
-    uint8_t* ebits = reinterpret_cast<uint8_t*>(lds_parent + HW);
+    // BFS edge test of every cell with its right neighbour (wrapping, IP:884-886) as a bit in LDS (ecol,
+    // after the parent words) — the union pass then reads LDS only (its global loads sat behind
+    // data-dependent branches). A wave takes a block of 64 columns, a lane the H <= 16 rows of one
+    // column, all loads in flight together: every range is read once, the upper neighbour is the
+    // lane's previous register and the right neighbour the next lane's value; only the column after
+    // the block (column 0 after the last: the wrap) is read again, a row per lane.
     constexpr int kH = 16;  // ccl_lds: H <= 16
-    const int ln = lane_id();
-    for (int j0 = (tid >> 6) * 64; j0 < W; j0 += nt) {
+    const int ln = lane_id(), wv = tid >> 6, nblk = (W + 63) >> 6;
+    unsigned short* ecol = reinterpret_cast<unsigned short*>(lds_parent + HW);  // column j: bit i = row i
+    for (int j0 = wv * 64; j0 < W; j0 += nt) {
       const int j = j0 + ln;
       const bool in = j < W;
-      const int jc = in ? j : W - 1, rows = in ? H : 0;
+      const int jc = in ? j : W - 1;
+      // (the rows as a per-lane value the compiler cannot see through: uniform tests of i against H
+      // would be hoisted out of the block loop as 32 lane masks, more scalar registers than there are)
+      // (likewise the 16 clamped row offsets: as products per lane they take no scalar registers)
+      int rows = in ? H : 0, hm = H - 1;
+      asm volatile("" : "+v"(rows), "+v"(hm));
       float r[kH];
       int8_t gv[kH];
 #pragma unroll
       for (int i = 0; i < kH; ++i) {  // (clamped, not predicated: cells outside are never used)
-        const int q = (i < H ? i : H - 1) * W + jc;
+        const int q = (i < hm ? i : hm) * W + jc;
         r[i] = rng[q];
         gv[i] = g[q];
       }
-      const float rx = ln < H ? rng[ln * W + (j0 + 64 < W ? j0 + 64 : 0)] : FLT_MAX;
-      // A wave holds 64 consecutive cells of row i: the right edges between neighbours inside the
-      // wave are resolved here, each cell pointing straight at the first cell of its linked run (the
-      // run's smallest index, so the union-find invariant "root = smallest cell" holds); only the
-      // wave's last right edge, the row wrap and the down edges are left for the union pass.
+      const int qx = (ln < H ? ln : 0) * W + (j0 + 64 < W ? j0 + 64 : 0);
+      const float rx = rng[qx];
+      const int8_t gx = g[qx];
+      // The lane walks down its column: the down links are a carry over its own registers, each cell
+      // pointing straight at the topmost cell of its vertical run (the run's smallest index, so the
+      // union-find invariant "root = smallest cell" holds). The right edge tests (the wrap included)
+      // are gathered as a row mask per column for the union pass; so is label 0, since a right edge
+      // counts only between two label-0 cells: the neighbour's mask comes from the next lane, at the
+      // block's edge from the column after it (lane i holds its row i).
+      const bool last = ln == 63 || j + 1 >= W;
+      unsigned m0 = 0, eb = 0, dm = 0;  // row masks: label 0, right edge test, linked to the cell above
+      int head = 0;
+      bool up = false;
 #pragma unroll
       for (int i = 0; i < kH; ++i) {
-        // (rows as a per-lane value: uniform tests of i against H would be hoisted out of the block
-        // loop as 32 lane masks, more scalar registers than there are)
-        const bool live = i < rows;
         const int cell = i * W + j;
         const float rn = __shfl_down(r[i], 1, 64), rw = __shfl(rx, i, 64);
-        const float rr = (ln == 63 || j + 1 >= W) ? rw : rn;
-        const bool l0 = live && !(gv[i] == 1 || r[i] == FLT_MAX);
-        const bool er = live && seg_edge(c, r[i], rr, true);
-        const bool ed = i + 1 < rows && seg_edge(c, r[i], i + 1 < kH ? r[i + 1] : FLT_MAX, false);
-        const bool l0n = __shfl_down(l0 ? 1 : 0, 1, 64) != 0;  // the next lane's cell (j + 1 if j + 1 < W)
-        const bool link = er && l0 && l0n && ln < 63 && j + 1 < W;  // resolved in the wave
-        const unsigned long long lk = __ballot(link);
-        const unsigned long long heads = ~(lk << 1);                 // lane 0 always starts a run
-        const int head = 63 - __clzll((long long)(heads & ((2ull << ln) - 1ull)));
-        if (!live) continue;
-        P.st(cell, l0 ? cell - (ln - head) : -1);
-        ebits[cell] = (uint8_t)((er && !link ? 1 : 0) | (ed ? 2 : 0));
+        const bool l0 = i < rows && !(gv[i] == 1 || r[i] == FLT_MAX);
+        if (seg_edge(c, r[i], last ? rw : rn, true)) eb |= 1u << i;
+        const bool dn = up && l0 && seg_edge(c, r[i > 0 ? i - 1 : 0], r[i], false);
+        if (!dn) head = cell;
+        if (dn) dm |= 1u << i;
+        up = l0;
+        if (l0) m0 |= 1u << i;
+        if (i < rows) P.st(cell, l0 ? head : -1);
       }
+      // the same two masks of the column after the block, from its lanes i - 1 and i
+      const bool l0x = ln < H && !(gx == 1 || rx == FLT_MAX);
+      const float rxu = __shfl_up(rx, 1, 64);
+      const bool l0xu = __shfl_up(l0x ? 1 : 0, 1, 64) != 0;
+      const unsigned mx = (unsigned)__ballot(l0x);
+      // (lane 0 tests its row against itself: bit 0 meets dm's, which is never set)
+      const unsigned dx = (unsigned)__ballot(l0x && l0xu && seg_edge(c, rxu, rx, false));
+      const unsigned mn = __shfl_down(m0, 1, 64), dn1 = __shfl_down(dm, 1, 64);
+      eb &= m0 & (last ? mx : mn);
+      // A right edge below another one between the same two vertical runs joins what is joined: only
+      // the topmost edge of such a ladder is kept (half of a VLP-16 scan's right edges go).
+      eb &= ~((eb << 1) & dm & (last ? dx : dn1));
+      if (in) ecol[j] = (unsigned short)eb;
     }
     __syncthreads();
     if (c.dbg_phase <= 0) return;
-    for (int cell = tid; cell < HW; cell += nt) {
-      const int e = ebits[cell];
-      if (e == 0 || P.ld(cell) < 0) continue;
-      const int i = cell / W, j = cell - i * W;
-      const int right = (j + 1 < W) ? cell + 1 : cell + 1 - W;  // wrap (IP:884-886)
-      if ((e & 1) && P.ld(right) >= 0) uf_unite(P, cell, right);
-      if ((e & 2) && P.ld(cell + W) >= 0) uf_unite(P, cell, cell + W);
+    // Union pass: right edges only, an item a row of a block of 64 columns. A wave gathers its items'
+    // edges into a queue of its own (the cell, bit 15 = its right neighbour is column 0) and unites
+    // 64 at a time, every lane busy: one lane in ten holds an edge, so a trip per item would run
+    // the find chains at a tenth of the wave. (A wave reads only what it wrote itself: LDS serves a
+    // wave's accesses in order.)
+    volatile unsigned short* q = ecol + ((W + 1) & ~1) + wv * 128;
+    int cnt = 0;
+    for (int w = wv, i = 0, k = wv; w < H * nblk; w += nt >> 6, k += nt >> 6) {
+      while (k >= nblk) k -= nblk, ++i;
+      const int j = k * 64 + ln;
+      const bool e = j < W && ((ecol[j] >> i) & 1);
+      const unsigned long long m = __ballot(e);
+      if (e) q[cnt + __popcll(m & ((1ull << ln) - 1ull))] = (unsigned short)((i * W + j) | (j + 1 < W ? 0 : 0x8000));
+      cnt += __popcll(m);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      if (cnt < 64) continue;
+      cnt -= 64;
+      const int v = q[cnt + ln], cell = v & 0x7fff;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      uf_unite(P, cell, cell + 1 - ((v & 0x8000) ? W : 0));  // wrap (IP:884-886)
+    }
+    if (ln < cnt) {
+      const int v = q[ln], cell = v & 0x7fff;
+      uf_unite(P, cell, cell + 1 - ((v & 0x8000) ? W : 0));
     }
     __syncthreads();
   } else {
