@@ -32,6 +32,7 @@ __global__ void k_vox_top(DevCfg, DevBufs, VoxRanges);
 __global__ void k_vox_leaf(DevCfg, DevBufs, VoxRanges);
 __global__ void k_vox_sum(DevCfg, DevBufs);
 __global__ void k_debug_exact_sort(const float*, int, int*);
+__global__ void k_debug_vox_keys(const float4*, int, int, uint32_t*, int*);
 __global__ void k_debug_half_passed(const float*, int, uint8_t*);
 __global__ void k_fa_concat(DevCfg, DevBufs);
 __global__ void k_dbscan_adj(DevCfg, DevBufs, const float4* __restrict__);
@@ -657,6 +658,44 @@ extern "C" int32_t llsr_debug_exact_sort32(const uint32_t* ranks, int32_t n, int
   return LLSR_OK;
 }
 
+// Diagnostics (not part of the ABI header): the PCL-order VoxelGrid's sort keys of one ring's worth
+// of candidate points, points[L][4] (x, y, z, intensity) with 1 <= L <= 2048, by the code
+// k_select_ring runs on a ring (vox_pcl_keys, in a kernel of its own): keys_out[t] = order << 11 | t
+// with `order` strictly increasing in the PCL voxel id of point t. *path_out = 0 where the keys came
+// from the row bitmap, 1 from the sorted runs (force_runs != 0 takes that path whatever the grid),
+// -1 where PCL's grid overflows and no keys are made. For tests/test_gpu_vox_keys.py.
+extern "C" int32_t llsr_debug_vox_keys(const float* points, int32_t L, int32_t force_runs, uint32_t* keys_out,
+                                       int32_t* path_out) {
+  if (!points || !keys_out || !path_out || L < 1 || L > 2048) return LLSR_EINVAL;
+  llsr_host::DevMem dp, dk, dq;
+  if (llsr_host::alloc(dp, sizeof(float4) * L) != hipSuccess || llsr_host::alloc(dk, sizeof(uint32_t) * L) != hipSuccess ||
+      llsr_host::alloc(dq, sizeof(int)) != hipSuccess)
+    return LLSR_ENODEV;
+  if (hipMemcpy(dp, points, sizeof(float4) * L, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(dk, 0, sizeof(uint32_t) * L) != hipSuccess)
+    return LLSR_EIO;
+  k_debug_vox_keys<<<1, 256>>>((const float4*)dp.get(), L, force_runs, (uint32_t*)dk.get(), (int*)dq.get());
+  int path = 0;
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(keys_out, dk, sizeof(uint32_t) * L, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&path, dq, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    return LLSR_EIO;
+  *path_out = path;
+  return LLSR_OK;
+}
+
+// Diagnostics (not part of the ABI header): out[b] = C_VOXRUNS of slot b of the last batch, the
+// number of its rings whose PCL-order keys came from the sorted runs (grid beyond the row bitmap).
+extern "C" int32_t llsr_debug_vox_runs(llsr_handle* h, int32_t* out) {
+  if (!h || !out) return LLSR_EINVAL;
+  int32_t rc = sync_last(h);
+  if (rc) return rc;
+  std::vector<int> cnt((size_t)h->last_B * kCnt);
+  HIP_OK(h, hipMemcpy(cnt.data(), h->d.counts, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int b = 0; b < h->last_B; ++b) out[b] = cnt[(size_t)b * kCnt + C_VOXRUNS];
+  return LLSR_OK;
+}
+
 // Diagnostics (not part of the ABI header): the DBSCAN merge and its run-length filter as a batch
 // runs them (k_dbscan_merge<kDbL>, kDbL 1024 or 2048) over n independent neighbourhood relations
 // given as host bit rows adj[n][kAdjCap][kAdjWords] (row i, bit j: j is a neighbour of i; only rows
@@ -752,6 +791,8 @@ extern "C" float llsr_debug_exact_sort_ms(const float* vals, int32_t n, int32_t 
 static void restore_selection(llsr_handle* h, int B, hipStream_t s) {
   const DevCfg& c = h->dc;
   launch_fa_points(c, h->d, B, s);
+  // (the diagnostic launches counted their run-path rings too: C_VOXRUNS starts over)
+  (void)hipMemset2DAsync(h->d.counts + C_VOXRUNS, sizeof(int) * kCnt, 0, sizeof(int), B, s);
   k_select_ring<<<dim3(c.H, B), 256, 0, s>>>(c, h->d);
   if (c.exact_vg) {
     (void)hipMemsetAsync(h->vox.count, 0, kVoxCntBytes, s);

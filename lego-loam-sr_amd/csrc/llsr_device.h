@@ -26,6 +26,7 @@ enum : int {
   C_HALF = 12,     // adjustDistortion halfPassed split index
   C_EXACT = 13,    // rings whose curvature sort took the exact libstdc++ path (ties)
   C_PHOUT = 14,    // rings where the carried cloudSmoothness[4] index fell outside the ring window
+  C_VOXRUNS = 15,  // rings whose PCL-order VoxelGrid keys came from the sorted runs (grid beyond the row bitmap)
   kCnt = 16
 };
 

@@ -444,6 +444,239 @@ __device__ __forceinline__ int greedy_wave(Order order, int nc, int ws, uint8_t*
   return nsel;
 }
 
+// ---- the less-flat VoxelGrid's voxel keys (k_select_ring; k_debug_vox_keys runs the same code) ----
+// A ring's candidates t = tid + 256 u sit in slot u of a lane (L <= kRingMax, 256 threads).
+constexpr int kRingLp = kRingMax / 256;
+// The row bitmap of the PCL-order keys: one bit per (i1, i2) row of the ring's voxel grid, in the
+// 16 KB of key[] (64-bit words; their 2048 prefixes are 16-bit and fill rstart[]). 128 Ki bits is
+// what that LDS holds; a bitmap counted in 32-bit words would need 4096 prefixes, twice rstart[],
+// and stop at 64 Ki. The bits are set through the words' 32-bit halves (little endian: bit r of
+// the bitmap is bit r & 31 of half r >> 5), one 32-bit LDS atomic per candidate.
+constexpr int kVoxRowBits = kRingMax * 64;
+constexpr int kVoxI0Bits = 10;  // i0 < div[0] <= 1024 below the row rank (< L <= 2048: 11 bits) and above the candidate (11)
+
+// The workgroup's LDS the key building works in: all of it k_select_ring's own, dead by then.
+struct VoxKeyLds {
+  uint64_t* key;     // [kRingMax]  bitmap path: the row bitmap; run path: the ids (vk), then the runs' sort keys
+  uint16_t* rstart;  // [kRingMax + 1]  bitmap path: the words' prefix counts; run path: the run starts
+  uint16_t* rrank;   // [kRingMax]  run path: run -> rank of its voxel id
+  int* scnt;         // [kRingLp * 4 + 1]
+  int* tmp;          // [4]
+};
+
+// PCL's bounds of the candidates in lpr (slot u valid when tid + 256 u < L); red: [6][4] floats.
+// Contains a barrier.
+__device__ __forceinline__ void vox_bounds(const float4 (&lpr)[kRingLp], int L, float (*red)[4], float (&mn)[3],
+                                           float (&mx)[3]) {
+  const int tid = threadIdx.x;
+  for (int a = 0; a < 3; ++a) { mn[a] = FLT_MAX; mx[a] = -FLT_MAX; }
+#pragma unroll
+  for (int u = 0; u < kRingLp; ++u) {
+    if (tid + u * 256 >= L) continue;
+    const float4 p = lpr[u];
+    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
+    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+  }
+  for (int a = 0; a < 3; ++a) { mn[a] = wave_reduce_min(mn[a]); mx[a] = wave_reduce_max(mx[a]); }
+  if (lane_id() == 0)
+    for (int a = 0; a < 3; ++a) { red[a][tid >> 6] = mn[a]; red[3 + a][tid >> 6] = mx[a]; }
+  __syncthreads();
+  for (int a = 0; a < 3; ++a) {
+    mn[a] = fminf(fminf(red[a][0], red[a][1]), fminf(red[a][2], red[a][3]));
+    mx[a] = fmaxf(fmaxf(red[3 + a][0], red[3 + a][1]), fmaxf(red[3 + a][2], red[3 + a][3]));
+  }
+}
+// PCL's grid of the bounds (leaf 0.2): false when it overflows an int (leaf too small -> output = input)
+__device__ __forceinline__ bool vox_grid(const float (&mn)[3], const float (&mx)[3], int (&minb)[3], int (&div)[3]) {
+  const float inv = 1.0f / 0.2f;
+  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1,
+                  dz = (long long)((mx[2] - mn[2]) * inv) + 1;
+  if (dx * dy * dz > (long long)INT_MAX) return false;
+  for (int a = 0; a < 3; ++a) {
+    minb[a] = (int)floorf(mn[a] * inv);
+    div[a] = (int)floorf(mx[a] * inv) - minb[a] + 1;
+  }
+  return true;
+}
+__device__ __forceinline__ void vox_cell(const float4 p, const int (&minb)[3], int& i0, int& i1, int& i2) {
+  const float inv = 1.0f / 0.2f;
+  i0 = (int)(floorf(p.x * inv) - (float)minb[0]);
+  i1 = (int)(floorf(p.y * inv) - (float)minb[1]);
+  i2 = (int)(floorf(p.z * inv) - (float)minb[2]);
+}
+// voxel id of every candidate, in ring order (points of one voxel are mostly consecutive): a lane's
+// own in vkr, all of them in vk[] = key[] for the run heads. Ends with a barrier.
+__device__ __forceinline__ void vox_ids(const float4 (&lpr)[kRingLp], int L, const int (&minb)[3], const int (&div)[3],
+                                        uint32_t (&vkr)[kRingLp], uint64_t* key) {
+  const int mul1 = div[0], mul2 = div[0] * div[1];
+  uint32_t* vk = reinterpret_cast<uint32_t*>(key);
+#pragma unroll
+  for (int u = 0; u < kRingLp; ++u) {
+    const int t = threadIdx.x + u * 256;
+    vkr[u] = 0u;
+    if (t >= L) continue;
+    int i0, i1, i2;
+    vox_cell(lpr[u], minb, i0, i1, i2);
+    vkr[u] = (uint32_t)(i0 + i1 * mul1 + i2 * mul2);
+    vk[t] = vkr[u];
+  }
+  __syncthreads();
+}
+// exclusive scan of scnt[0 .. kRingLp*4) in place, total in scnt[kRingLp*4]
+__device__ __forceinline__ void vox_slot_scan(int* scnt) {
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int ln = threadIdx.x;
+    const int v = ln < kRingLp * 4 ? scnt[ln] : 0;
+    const int incl = wave_incl_scan_add(v);
+    if (ln < kRingLp * 4) scnt[ln] = incl - v;
+    if (ln == 63) scnt[kRingLp * 4] = incl;
+  }
+  __syncthreads();
+}
+// runs of equal voxel id in ring order (after vox_ids) -> one sort key per run, (voxel id, run
+// index), sorted (block4_sort); run starts in rstart. Position t = u * 256 + tid in slot u of a
+// lane; run indices from per-(slot, wave) ballot counts scanned in (slot, wave) = ring order.
+// (Every key[] write comes after the barrier that ends the vk[] reads.) Returns the run count.
+__device__ __forceinline__ int vox_sort_runs(const uint32_t (&vkr)[kRingLp], int L, const VoxKeyLds& s) {
+  const int tid = threadIdx.x, wv = tid >> 6, ln = lane_id();
+  const unsigned long long ltm = (1ull << ln) - 1ull;
+  const uint32_t* vk = reinterpret_cast<const uint32_t*>(s.key);
+  unsigned long long mR[kRingLp];
+#pragma unroll
+  for (int u = 0; u < kRingLp; ++u) {
+    const int t = u * 256 + tid;
+    mR[u] = __ballot(t < L && (t == 0 || vkr[u] != vk[t - 1]));
+    if (ln == 0) s.scnt[u * 4 + wv] = (int)__popcll(mR[u]);
+  }
+  vox_slot_scan(s.scnt);
+  const int R = s.scnt[kRingLp * 4];
+#pragma unroll
+  for (int u = 0; u < kRingLp; ++u) {
+    if (!((mR[u] >> ln) & 1ull)) continue;
+    const int t = u * 256 + tid;
+    const int ro = s.scnt[u * 4 + wv] + (int)__popcll(mR[u] & ltm);
+    s.rstart[ro] = (uint16_t)t;
+    s.key[ro] = ((uint64_t)vkr[u] << 32) | (uint32_t)ro;
+  }
+  if (tid == 0) s.rstart[R] = (uint16_t)L;
+  const int R2 = max(pow2_ceil(R), 64);
+  for (int t = R + tid; t < R2; t += 256) s.key[t] = ~0ull;
+  __syncthreads();
+  block4_sort<uint64_t>(s.key, R2);
+  return R;
+}
+
+// The PCL-order sort keys of a ring's candidates, gk[t] = order << 11 | t for t < L: `order`
+// (< 2^21) is any strictly increasing map of the ring's voxel ids, since the sort (VoxLess32) and
+// k_vox_sum read nothing but the outcome of comparing those bits. The id i0 + i1 dx + i2 dx dy
+// with i0 < dx, i1 < dy orders like (i2, i1, i0), so:
+//   0  row bitmap (dx <= 1024 and dy dz <= kVoxRowBits): order = rank of the row i1 + i2 dy among
+//      the ring's occupied rows << 10 | i0. The rows are marked in a bitmap in key[] (only its
+//      dy dz bits are cleared and counted), a row's rank is the popcount below its bit, and every
+//      candidate stores its own key: coalesced stores, four barriers.
+//   1  sorted runs (any grid): order = the dense rank of the id, from the runs of equal ids sorted
+//      by id; one thread per run stores its run's keys.
+// Returns the path taken (uniform). force_runs: diagnostics only.
+__device__ __forceinline__ int vox_pcl_keys(const float4 (&lpr)[kRingLp], int L, const int (&minb)[3],
+                                            const int (&div)[3], bool force_runs, const VoxKeyLds& s, uint32_t* gk) {
+  const int tid = threadIdx.x, wv = tid >> 6, ln = lane_id();
+  const long long rows = (long long)div[1] * div[2];
+  if (!force_runs && div[0] <= (1 << kVoxI0Bits) && rows <= kVoxRowBits) {
+    const int nW = ((int)rows + 63) >> 6;
+    for (int w = tid; w < nW; w += 256) s.key[w] = 0ull;
+    // (finite points lie inside their own bounds; the clamps keep any other input inside the bitmap)
+    uint32_t row[kRingLp], i0r[kRingLp];
+#pragma unroll
+    for (int u = 0; u < kRingLp; ++u) {
+      row[u] = i0r[u] = 0u;
+      if (tid + u * 256 >= L) continue;
+      int i0, i1, i2;
+      vox_cell(lpr[u], minb, i0, i1, i2);
+      row[u] = min((uint32_t)(i1 + i2 * div[1]), (uint32_t)rows - 1u);
+      i0r[u] = min((uint32_t)i0, (1u << kVoxI0Bits) - 1u);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kRingLp; ++u)
+      if (tid + u * 256 < L)
+        atomicOr(reinterpret_cast<uint32_t*>(s.key) + (row[u] >> 5), 1u << (row[u] & 31u));
+    __syncthreads();
+    // every thread counts a contiguous share of the words; the words' prefixes to rstart[]
+    const int per = (nW + 255) >> 8;
+    const int w0 = min(tid * per, nW), w1 = min(w0 + per, nW);
+    int cnt = 0;
+    for (int w = w0; w < w1; ++w) cnt += (int)__popcll(s.key[w]);
+    const int incl = wave_incl_scan_add(cnt);
+    if (ln == 63) s.tmp[wv] = incl;
+    __syncthreads();
+    int pre = incl - cnt;
+    for (int k = 0; k < wv; ++k) pre += s.tmp[k];
+    for (int w = w0; w < w1; ++w) {
+      s.rstart[w] = (uint16_t)pre;
+      pre += (int)__popcll(s.key[w]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kRingLp; ++u) {
+      const int t = tid + u * 256;
+      if (t >= L) continue;
+      const uint64_t wd = s.key[row[u] >> 6];
+      const uint32_t rr = (uint32_t)s.rstart[row[u] >> 6] + (uint32_t)__popcll(wd & ((1ull << (row[u] & 63u)) - 1ull));
+      gk[t] = (((rr << kVoxI0Bits) | i0r[u]) << 11) | (uint32_t)t;
+    }
+    return 0;
+  }
+  uint32_t vkr[kRingLp];
+  vox_ids(lpr, L, minb, div, vkr, s.key);
+  const int R = vox_sort_runs(vkr, L, s);
+  const unsigned long long lem = ((1ull << ln) - 1ull) | (1ull << ln);
+  unsigned long long mH[kRingLp];
+#pragma unroll
+  for (int u = 0; u < kRingLp; ++u) {
+    const int t = u * 256 + tid;
+    mH[u] = __ballot(t < R && (t == 0 || (s.key[t] >> 32) != (s.key[t - 1] >> 32)));
+    if (ln == 0) s.scnt[u * 4 + wv] = (int)__popcll(mH[u]);
+  }
+  vox_slot_scan(s.scnt);
+#pragma unroll
+  for (int u = 0; u < kRingLp; ++u) {
+    const int t = u * 256 + tid;
+    if (t < R) s.rrank[(uint32_t)s.key[t]] = (uint16_t)(s.scnt[u * 4 + wv] + (int)__popcll(mH[u] & lem) - 1);
+  }
+  __syncthreads();
+  for (int r = tid; r < R; r += 256) {
+    const uint32_t rk = (uint32_t)s.rrank[r] << 11;
+    const int qe = s.rstart[r + 1];
+    for (int q = s.rstart[r]; q < qe; ++q) gk[q] = rk | (uint32_t)q;
+  }
+  return 1;
+}
+
+// Diagnostics (llsr_debug_vox_keys): vox_pcl_keys on L <= kRingMax caller-given candidate points as
+// k_select_ring runs it on a ring's; path receives the path taken, -1 where PCL's grid overflows.
+__global__ __launch_bounds__(256) void k_debug_vox_keys(const float4* pts, int L, int force_runs, uint32_t* keys,
+                                                        int* path) {
+  __shared__ uint64_t key[kRingMax];
+  __shared__ uint16_t rstart[kRingMax + 1], rrank[kRingMax];
+  __shared__ int scnt[kRingLp * 4 + 1], tmp[8];
+  __shared__ float red[6][4];
+  const int tid = threadIdx.x;
+  float4 lpr[kRingLp];
+#pragma unroll
+  for (int u = 0; u < kRingLp; ++u)
+    if (tid + u * 256 < L) lpr[u] = pts[tid + u * 256];
+  float mn[3], mx[3];
+  vox_bounds(lpr, L, red, mn, mx);
+  int minb[3], div[3];
+  if (!vox_grid(mn, mx, minb, div)) {
+    if (tid == 0) *path = -1;
+    return;
+  }
+  const int p = vox_pcl_keys(lpr, L, minb, div, force_runs != 0, VoxKeyLds{key, rstart, rrank, scnt, tmp}, keys);
+  if (tid == 0) *path = p;
+}
+
 __global__ __launch_bounds__(256, 5) void k_select_ring(DevCfg c, DevBufs d) {
   // LDS < 32 KB -> 5 workgroups per CU. The window keeps two bytes per position: a flag byte
   // (suppression reach forward | backward << 3 (FA:1186-1205), ground << 6, picked << 7) and the
@@ -718,146 +951,56 @@ __global__ __launch_bounds__(256, 5) void k_select_ring(DevCfg c, DevBufs d) {
   const float4* lp = d.loam + base + sp;
   // ---- VoxelGrid(0.2) applyFilter (PCL 1.10), centroids summed in (voxel, input) order ----
   // each lane's candidates (t = tid + 256 u, L <= 2048) are gathered once, for the bounds and the keys
-  constexpr int kLp = kRingMax / 256;
+  constexpr int kLp = kRingLp;
   float4 lpr[kLp];
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
 #pragma unroll
   for (int u = 0; u < kLp; ++u)
     if (tid + u * 256 < L) lpr[u] = lp[cpos[tid + u * 256]];
-#pragma unroll
-  for (int u = 0; u < kLp; ++u) {
-    if (tid + u * 256 >= L) continue;
-    const float4 p = lpr[u];
-    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-  }
-  for (int a = 0; a < 3; ++a) { mn[a] = wave_reduce_min(mn[a]); mx[a] = wave_reduce_max(mx[a]); }
-  if (lane_id() == 0)
-    for (int a = 0; a < 3; ++a) { red[a][tid >> 6] = mn[a]; red[3 + a][tid >> 6] = mx[a]; }
-  __syncthreads();
-  for (int a = 0; a < 3; ++a) {
-    mn[a] = fminf(fminf(red[a][0], red[a][1]), fminf(red[a][2], red[a][3]));
-    mx[a] = fmaxf(fmaxf(red[3 + a][0], red[3 + a][1]), fmaxf(red[3 + a][2], red[3 + a][3]));
-  }
-  const float inv = 1.0f / 0.2f;
+  float mn[3], mx[3];
+  vox_bounds(lpr, L, red, mn, mx);
   float4* out = d.lflat_tmp + base + sp;
   if (L == 0) {
     if (tid == 0) rc[2 * H + i] = 0;
     return;
   }
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1,
-                  dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-  if (dx * dy * dz > (long long)INT_MAX) {  // PCL: leaf too small -> output = input
+  int minb[3], div[3];
+  if (!vox_grid(mn, mx, minb, div)) {  // PCL: leaf too small -> output = input
     for (int t = tid; t < L; t += nt) out[t] = lp[cpos[t]];
     if (tid == 0) rc[2 * H + i] = L;
     return;
   }
-  int minb[3], div[3];
-  for (int a = 0; a < 3; ++a) {
-    minb[a] = (int)floorf(mn[a] * inv);
-    div[a] = (int)floorf(mx[a] * inv) - minb[a] + 1;
-  }
-  const int mul1 = div[0], mul2 = div[0] * div[1];
-  // voxel id of every candidate, in ring order (points of one voxel are mostly consecutive)
-  // (in key[]: dead after the greedy passes; every key[] write below comes after the barriers that
-  // end the vk[] reads, and a lane's own ids stay in vkr)
-  uint32_t* vk = reinterpret_cast<uint32_t*>(key);
-  uint32_t vkr[kLp];
-#pragma unroll
-  for (int u = 0; u < kLp; ++u) {
-    const int t = tid + u * 256;
-    vkr[u] = 0u;
-    if (t >= L) continue;
-    const float4 p = lpr[u];
-    const int i0 = (int)(floorf(p.x * inv) - (float)minb[0]);
-    const int i1 = (int)(floorf(p.y * inv) - (float)minb[1]);
-    const int i2 = (int)(floorf(p.z * inv) - (float)minb[2]);
-    vkr[u] = (uint32_t)(i0 + i1 * mul1 + i2 * mul2);
-    vk[t] = vkr[u];
-  }
-  __syncthreads();
+  // (the voxel keys work in key[], dead after the greedy passes, rstart[] and, on the run path of
+  // the PCL order, the window's storage)
   __shared__ int scnt[kLp * 4 + 1];
+  const VoxKeyLds vl{key, rstart, reinterpret_cast<uint16_t*>(win_raw), scnt, tmp};
   const int wv = tid >> 6, ln = lane_id();
   const unsigned long long ltm = (1ull << ln) - 1ull;
   int V;
-  auto slot_scan = [&]() {  // exclusive scan of scnt[0 .. kLp*4) in place, total in scnt[kLp*4]
-    __syncthreads();
-    if (wv == 0) {
-      const int v = ln < kLp * 4 ? scnt[ln] : 0;
-      const int incl = wave_incl_scan_add(v);
-      if (ln < kLp * 4) scnt[ln] = incl - v;
-      if (ln == 63) scnt[kLp * 4] = incl;
-    }
-    __syncthreads();
-  };
-  // runs of equal voxel id in ring order -> one sort key per run, (voxel id, run index), sorted
-  // (block4_sort); run starts in rstart. Position t = u * 256 + tid in slot u of a lane; run
-  // indices from per-(slot, wave) ballot counts scanned in (slot, wave) = ring order.
-  auto sort_runs = [&]() {
-    unsigned long long mR[kLp];
-#pragma unroll
-    for (int u = 0; u < kLp; ++u) {
-      const int t = u * 256 + tid;
-      mR[u] = __ballot(t < L && (t == 0 || vkr[u] != vk[t - 1]));
-      if (ln == 0) scnt[u * 4 + wv] = (int)__popcll(mR[u]);
-    }
-    slot_scan();
-    const int R = scnt[kLp * 4];
-#pragma unroll
-    for (int u = 0; u < kLp; ++u) {
-      if (!((mR[u] >> ln) & 1ull)) continue;
-      const int t = u * 256 + tid;
-      const int ro = scnt[u * 4 + wv] + (int)__popcll(mR[u] & ltm);
-      rstart[ro] = (uint16_t)t;
-      key[ro] = ((uint64_t)vkr[u] << 32) | (uint32_t)ro;
-    }
-    if (tid == 0) rstart[R] = (uint16_t)L;
-    const int R2 = max(pow2_ceil(R), 64);
-    for (int t = R + tid; t < R2; t += nt) key[t] = ~0ull;
-    __syncthreads();
-    block4_sort<uint64_t>(key, R2);
-    return R;
-  };
   if (c.exact_vg) {
     // LLSR_VOXEL_ORDER_PCL (llsr_set_voxel_order): std::sort(index_vector) by voxel id alone (PCL
     // 1.10 voxel_grid.hpp) and the centroids summed in that order run in kernels of their own
-    // (k_vox_top / k_vox_leaf / k_vox_sum below). They
-    // sort 32-bit keys (rank << 11 | candidate): each voxel id replaced by its dense rank among the
-    // ring's ids, which keeps the outcome of every comparison; the ranks come from the sorted voxel
-    // runs. The keys and the candidate positions go to the scratch slots of the ring's positions
-    // (ccl_a / ccl_b, dead since k_label), and rc[2H + i] = -1 - L marks the ring pending.
+    // (k_vox_top / k_vox_leaf / k_vox_sum below). They sort 32-bit keys (order << 11 | candidate):
+    // each voxel id replaced by a 21-bit number that keeps the outcome of every comparison
+    // (vox_pcl_keys: from a bitmap of the grid's occupied rows, or from the sorted voxel runs where
+    // the grid is beyond the bitmap; C_VOXRUNS counts those rings). The keys and the candidate
+    // positions go to the scratch slots of the ring's positions (ccl_a / ccl_b, dead since
+    // k_label), and rc[2H + i] = -1 - L marks the ring pending.
     if (c.dbg_phase <= 5) return;
-    const int R = sort_runs();
-    uint16_t* rrank = reinterpret_cast<uint16_t*>(win_raw);  // run -> rank of its voxel id
-    const unsigned long long lem = ltm | (1ull << ln);
-    unsigned long long mH[kLp];
-#pragma unroll
-    for (int u = 0; u < kLp; ++u) {
-      const int t = u * 256 + tid;
-      mH[u] = __ballot(t < R && (t == 0 || (key[t] >> 32) != (key[t - 1] >> 32)));
-      if (ln == 0) scnt[u * 4 + wv] = (int)__popcll(mH[u]);
-    }
-    slot_scan();
-#pragma unroll
-    for (int u = 0; u < kLp; ++u) {
-      const int t = u * 256 + tid;
-      if (t < R) rrank[(uint32_t)key[t]] = (uint16_t)(scnt[u * 4 + wv] + (int)__popcll(mH[u] & lem) - 1);
-    }
-    __syncthreads();
     uint32_t* gk = reinterpret_cast<uint32_t*>(d.ccl_a + base) + sp;
     uint16_t* gc = reinterpret_cast<uint16_t*>(d.ccl_b + base) + sp;
-    for (int r = tid; r < R; r += nt) {
-      const uint32_t rk = (uint32_t)rrank[r] << 11;
-      const int qe = rstart[r + 1];
-      for (int q = rstart[r]; q < qe; ++q) gk[q] = rk | (uint32_t)q;
-    }
+    const int path = vox_pcl_keys(lpr, L, minb, div, false, vl, gk);
     for (int t = tid; t < L; t += nt) gc[t] = cpos[t];
-    if (tid == 0) rc[2 * H + i] = -1 - L;
+    if (tid == 0) {
+      rc[2 * H + i] = -1 - L;
+      if (path) atomicAdd(&d.counts[b * kCnt + C_VOXRUNS], 1);
+    }
     return;
   } else {
     // LLSR_VOXEL_ORDER_INPUT: each voxel summed run by run in ring order (sorted runs)
+    uint32_t vkr[kLp];
+    vox_ids(lpr, L, minb, div, vkr, key);
     if (c.dbg_phase <= 5) return;
-    const int R = sort_runs();
+    const int R = vox_sort_runs(vkr, L, vl);
     if (c.dbg_phase <= 6) return;
     // voxels = groups of sorted runs with equal id; sum members in (run start, position) order.
     // Sorted run t = u * 256 + tid sits in slot u of a lane, so a wave's voxel heads of one slot are
@@ -871,7 +1014,7 @@ __global__ __launch_bounds__(256, 5) void k_select_ring(DevCfg c, DevBufs d) {
       mH[u] = __ballot(head);
       if (ln == 0) scnt[u * 4 + wv] = (int)__popcll(mH[u]);
     }
-    slot_scan();
+    vox_slot_scan(scnt);
     V = scnt[kLp * 4];
 #pragma unroll
     for (int u = 0; u < kLp; ++u) {
