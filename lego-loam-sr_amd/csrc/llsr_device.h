@@ -321,4 +321,17 @@ __host__ __device__ __forceinline__ int trunc_i32(double v) {
   return (int)v;
 }
 
+// PCL 1.10 RandomSampleConsensus::computeModel's iteration bound after a best model of `cnt` inliers
+// among the K points behind one_over = 1 / K: k = log(1 - p) / log(1 - w^3), w = cnt / K, with
+// 1 - w^3 held inside [eps, 1 - eps]. log and pow are the compiling side's own libm (ocml in a
+// kernel); DESIGN.md §2 holds the measured margin that makes their last bits harmless.
+// k_ground_elev_ransac and llsr_debug_ransac_k (llsr_math_debug.hip) both call this.
+__host__ __device__ __forceinline__ double ransac_k(int cnt, double one_over, double log_probability) {
+  const double w = (double)cnt * one_over;
+  double p_no = 1.0 - pow(w, 3.0);
+  p_no = fmax(2.220446049250313e-16, p_no);
+  p_no = fmin(1.0 - 2.220446049250313e-16, p_no);
+  return log_probability / log(p_no);
+}
+
 }  // namespace llsr

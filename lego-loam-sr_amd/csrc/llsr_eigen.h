@@ -12,7 +12,9 @@
 // no FMA — including the order in which each reduction adds (the kernel Eigen dispatches to
 // decides it: Redux.h, GeneralMatrixVector.h, SelfadjointMatrixVector.h, ProductEvaluators.h).
 // The oracle restates the same routines independently (oracle/oracle_eigen.h); the two are
-// cross-checked bit for bit on random and rank-deficient matrices by tests/test_eigen_restatement.py.
+// cross-checked bit for bit on random and rank-deficient matrices by tests/test_eigen_restatement.py
+// (this text as g++ compiles it) and, routine by routine in a kernel, by
+// tests/test_gpu_math_headers.py (the gfx950 compile, through llsr_math_debug.hip).
 //
 // Every loop has a compile-time trip count (or is fully unrolled), so on the device the matrices
 // stay in registers; runtime column indices are replaced by compare-and-select.

@@ -946,11 +946,7 @@ __global__ __launch_bounds__(1024) void k_ground_elev_ransac(DevCfg c, DevBufs d
         sh_int[3] = cnt;
         for (int q = 0; q < 4; ++q) best_cf[q] = cf[q];
         sh_int[5] = 1;
-        const double w = (double)cnt * one_over;
-        double p_no = 1.0 - pow(w, 3.0);
-        p_no = fmax(2.220446049250313e-16, p_no);
-        p_no = fmin(1.0 - 2.220446049250313e-16, p_no);
-        kk = log_probability / log(p_no);
+        kk = ransac_k(cnt, one_over, log_probability);
       }
       sh_int[2] += 1;
       if (sh_int[2] > 10000) sh_int[0] = 1;

@@ -24,7 +24,10 @@
 //
 // Validation: oracle/libm_check.cpp compares every function against the host glibc over all
 // 2^32 float inputs (asinf, acosf, atanf; tanf, sinf, cosf on |x| < 120) and over dense
-// random/structured pairs for atan2f. See DESIGN.md §2.
+// random/structured pairs for atan2f; that is this text as g++ compiles it. The gfx950 compile is
+// run function by function (llsr_math_debug.hip) by tests/test_gpu_math_headers.py, which holds a
+// kernel's bits to the host compile's and to glibc's on a strided sweep and at every branch
+// constant below. See DESIGN.md §2.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -53,13 +56,7 @@ LLSR_HD float bitsf(uint32_t u) {
 }
 LLSR_HD float fabs_(float x) { return bitsf(fbits(x) & 0x7fffffffu); }
 // IEEE correctly-rounded single sqrt on both sides.
-LLSR_HD float sqrt_(float x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_sqrtf(x);
-#else
-  return __builtin_sqrtf(x);
-#endif
-}
+LLSR_HD float sqrt_(float x) { return __builtin_sqrtf(x); }
 
 // ---- asinf: glibc e_asinf.c (x + x^3 p(x^2) form, pio2_hi rounded up) ----------------------
 LLSR_HD float asinf_(float x) {

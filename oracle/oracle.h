@@ -84,6 +84,13 @@ int32_t oracle_eig3(const float* A, float* evals, float* evecs);
 int32_t oracle_eig6(const float* A, float* evals, float* evecs);
 void oracle_qr_solve_5x3(const float* A, const float* b, float* x);
 void oracle_qr_solve_6x6(const float* A, const float* b, float* x);
+/* Batch references for the product's numeric headers (oracle_math.cpp; selectors and packing there):
+ * glibc's float and double elementary functions, the Eigen restatement over n packed cases, and
+ * the iteration bound k of PlaneRansac::run (oracle_ipfa.cpp) for n pairs (K points, cnt inliers). */
+int32_t oracle_libm_f32(int32_t fn, int64_t n, const float* x, const float* y, float* out);
+int32_t oracle_libm_f64(int32_t fn, int64_t n, const double* x, const double* y, double* out);
+int32_t oracle_eigen_batch(int32_t op, int64_t n, const float* in, float* out, int32_t* info);
+void oracle_ransac_k(int64_t n, const int32_t* K, const int32_t* cnt, double* out);
 
 /* pcl::VoxelGrid<PointXYZI>::filter (oracle_voxel.h) of n float4 points; returns the centroid
  * count written to `out` (capacity n float4), -1 on bad arguments. stable != 0 sums each voxel in

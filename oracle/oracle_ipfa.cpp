@@ -30,6 +30,17 @@ inline int trunc_i32(double v) {
   return (int)v;
 }
 
+// RandomSampleConsensus::computeModel's iteration bound k after a best model of `best` inliers
+// (ransac.hpp: w, p_no_outliers clamped into [eps, 1 - eps], k = log(1 - p) / log(p_no_outliers)),
+// with glibc's log and pow. PlaneRansac::run and the oracle_ransac_k hook both call it.
+inline double ransac_k(int best, double one_over_indices, double log_probability) {
+  double w = (double)best * one_over_indices;
+  double p_no = 1.0 - std::pow(w, 3.0);
+  p_no = std::max(std::numeric_limits<double>::epsilon(), p_no);
+  p_no = std::min(1.0 - std::numeric_limits<double>::epsilon(), p_no);
+  return log_probability / std::log(p_no);
+}
+
 // ------------------------------------------------------------------------------------------
 // PCL 1.10 RandomSampleConsensus<PointXYZI> with SampleConsensusModelPlane (IP:716-721).
 // Model RNG: boost::mt19937 seeded 12345 per model instance, drawn through
@@ -116,11 +127,7 @@ struct PlaneRansac {
         best = cnt;
         std::memcpy(bestc, c, sizeof bestc);
         have = true;
-        double w = (double)best * one_over_indices;
-        double p_no = 1.0 - std::pow(w, 3.0);
-        p_no = std::max(std::numeric_limits<double>::epsilon(), p_no);
-        p_no = std::min(1.0 - std::numeric_limits<double>::epsilon(), p_no);
-        k = log_probability / std::log(p_no);
+        k = ransac_k(best, one_over_indices, log_probability);
       }
       ++iterations;
       if (iterations > max_iterations) break;
@@ -235,6 +242,12 @@ extern "C" void oracle_std_sort_by_value(const float* vals, int32_t n, int32_t* 
 // cloudSmoothness[4].ind, the entry the next frame's ring-0 sort starts from (test hook)
 extern "C" int32_t oracle_phantom_index(const oracle_state* s) { return (int32_t)s->smooth[4].second; }
 extern "C" void oracle_set_voxel_order(oracle_state* s, int32_t pcl) { s->vg_stable = pcl == 0; }
+
+// k of PlaneRansac::run for n pairs (K points, a best model of cnt inliers), as run() sets them up
+extern "C" void oracle_ransac_k(int64_t n, const int32_t* K, const int32_t* cnt, double* out) {
+  const double log_probability = std::log(1.0 - 0.99);
+  for (int64_t q = 0; q < n; ++q) out[q] = ransac_k(cnt[q], 1.0 / (double)K[q], log_probability);
+}
 
 extern "C" int32_t oracle_ransac_inliers(oracle_state* s, uint32_t seed, int32_t* out, int32_t cap) {
   PlaneRansac rs(s->near, seed);

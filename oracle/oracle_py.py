@@ -30,7 +30,8 @@ def lib():
     if _LIB is None:
         path = os.path.join(_HERE, "_build", "liboracle.so")
         srcs = [os.path.join(_HERE, f) for f in ("oracle_ipfa.cpp", "oracle_mo.cpp", "oracle_fa_lm.cpp",
-                                                        "oracle_map.cpp", "oracle_mapping.cpp", "oracle_voxel.h")]
+                                                        "oracle_map.cpp", "oracle_mapping.cpp", "oracle_math.cpp",
+                                                        "oracle_voxel.h")]
         if not os.path.exists(path) or os.path.getmtime(path) < max(map(os.path.getmtime, srcs)):
             build()
         L = C.CDLL(path)
@@ -52,6 +53,12 @@ def lib():
             getattr(L, f).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         for f in ("oracle_qr_solve_5x3", "oracle_qr_solve_6x6"):
             getattr(L, f).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        for f in ("oracle_libm_f32", "oracle_libm_f64"):
+            getattr(L, f).restype = C.c_int32
+            getattr(L, f).argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_eigen_batch.restype = C.c_int32
+        L.oracle_eigen_batch.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_ransac_k.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         _bind_mo(L, "oracle_")
         L.oracle_transform_to_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.oracle_shadow_points.argtypes = [C.c_void_p]
